@@ -12,13 +12,29 @@ N>1 each rank searches its own ~1 M-sequence slice of an N M-sequence DB
 logs are gathered to rank 0 over RCCL and replayed there (ssa_amd_replay),
 giving the bit-exact global result.
 
-The same JSON line carries a "north_star" record (BASELINE.json north_star):
-SW int16, the same query against the FIXED 10 M-sequence DB (the c4full
-fixture), cut into N residue-balanced ID slices -- the strong-scaling point
-the driver's `--gpus 1/2/4/8` runs produce, top-k checked against the
-reference's own search of that DB.  --no-north-star skips it.
+A plain run does only what the headline figure needs: it sets the workload
+up, runs W warm-up steps, times K steps and prints one JSON line (metric,
+value, unit, higher_is_better, dtype, ms_per_step = the milliseconds one timed
+step took, and what the timed steps' own counters give for free).  With
+--dump-outputs DIR it also writes what the last timed step returned to its
+caller -- the top-k hits, best first -- as DIR/topk_scores.npy and
+DIR/topk_ids.npy (float64, k values each); the workload is seeded, so two
+builds run with the same arguments can be compared output for output.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|ref|sprot|north_star] [--seqs S]
+--full adds everything else to the same line, as measurements of their own
+after the timed steps: the host-side breakdown of one search (host_ms), the
+top-k against the reference's stored search of the same DB
+(topk_vs_reference), the reference's AVX2 kernel timed on the host CPU
+(cpu_baseline; --no-cpu-baseline skips it), at N > 1 the RCCL gather checked
+against the torch.distributed gather and the drop_in record (--no-drop-in
+skips it), and a "north_star" record (BASELINE.json north_star): SW int16, the
+same query against the FIXED 10 M-sequence DB (the c4full fixture), cut into N
+residue-balanced ID slices -- the strong-scaling point the driver's
+`--gpus 1/2/4/8` runs produce, top-k checked against the reference's own
+search of that DB.  --no-north-star skips it.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                    [--config c2|c3|c4|c5|ref|sprot|north_star] [--seqs S]
 
 Launch: under torchrun (WORLD_SIZE set) every process is one rank.  Without
 it, `--gpus N` with N > 1 makes this process a launcher that never imports
@@ -92,6 +108,12 @@ def parse():
     p.add_argument("--gap-open", type=int, default=None)
     p.add_argument("--gap-extend", type=int, default=None)
     p.add_argument("--k", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also measure and check everything else the line can carry: "
+                        "host_ms breakdown, topk_vs_reference, cpu_baseline, north_star, at N>1 the gather "
+                        "check and drop_in")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the last timed step's top-k to DIR/topk_scores.npy and DIR/topk_ids.npy (float64)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=15.0)
     p.add_argument("--no-north-star", action="store_true",
@@ -125,6 +147,8 @@ def parse():
     p.add_argument("--selftest-fail-rank", type=int, default=-1,
                    help="--launch-selftest: this rank exits with status 3 before the rendezvous")
     args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     return args
 
 
@@ -527,9 +551,12 @@ def lean_events_on():
     return _OPTIONS.get("lean_events", 1) != 0
 
 
-def timed_steps(S, job, sh, w, steps, warmup, k):
+def timed_steps(S, job, sh, w, steps, warmup, k, full=True):
     """W untimed warm-up steps, then exactly K steps between barrier +
-    synchronize on both sides; the max over ranks of the elapsed time."""
+    synchronize on both sides; the max over ranks of the elapsed time.  The
+    result is the last timed step's.  full: the measurements of their own
+    (N > 1: the gather check before the timed steps; the host breakdown of
+    one more search after them)."""
     algo = S.SW if w.algo == "sw" else S.NW
     # N > 1: the host clock around each step's search and gather, on every
     # rank (two perf_counter reads per step; they add nothing measurable)
@@ -540,8 +567,9 @@ def timed_steps(S, job, sh, w, steps, warmup, k):
             # the public sw_align / nw_align + free_alignment (libssa.h).  The
             # timed loop calls them exactly as the reference's benchmark does,
             # free_alignment(sw_align(...)) with the hits unread
-            # (benchmark/src/benchmark_util.c:27-48); the result is read from
-            # one more, untimed search of the same query after the loop
+            # (benchmark/src/benchmark_util.c:27-48); only the last timed
+            # step reads its hits' (score, ID) between the two calls (a few
+            # microseconds), so the result reported is the timed path's own
             if not keep:
                 S.align_free(sh.qq, k, w.width, algo)
                 return None
@@ -560,7 +588,7 @@ def timed_steps(S, job, sh, w, steps, warmup, k):
 
     for _ in range(warmup):
         step()
-    if job.native and job.gather_checked is None:
+    if full and job.native and job.gather_checked is None:
         check_native_gather(S, job, sh.qq, algo, k, w.width)
     split["search_s"].clear()
     split["gather_s"].clear()
@@ -569,13 +597,11 @@ def timed_steps(S, job, sh, w, steps, warmup, k):
     st0 = S.stats()
     job.sync()
     t_start = time.perf_counter()
-    for _ in range(steps):
-        res = step(keep=job.world > 1)
+    for i in range(steps):
+        res = step(keep=job.world > 1 or i == steps - 1)
     job.sync()
     elapsed = job.max(time.perf_counter() - t_start)
     st = S.stats()
-    if job.world == 1:
-        res = step()
     n = st["total_searches"] - st0["total_searches"]
     if n > 0:
         avg = {"kernel_ms": (st["total_kernel_ms"] - st0["total_kernel_ms"]) / n,
@@ -586,15 +612,16 @@ def timed_steps(S, job, sh, w, steps, warmup, k):
     # (host-side breakdown: the last search's.  The timing markers around the
     # upload, the re-score tier and the filter are off by default (option
     # lean_events: they cost ~40 us a search), so one extra untimed local
-    # search with them on fills in the breakdown)
+    # search with them on fills in the breakdown: --full only)
     lean = lean_events_on()
-    if lean:
+    if lean and full:
         S.set_option("lean_events", 0)
         S.align_scores(sh.qq, k, w.width, algo)
         S.set_option("lean_events", 1)
-    sb = S.stats() if lean else st
-    for f in ("wide_ms", "prep_ms", "upload_ms", "sync_wait_ms", "d2h_ms", "replay_ms"):
-        avg[f] = sb[f]
+    if full or not lean:
+        sb = S.stats() if lean else st
+        for f in ("wide_ms", "prep_ms", "upload_ms", "sync_wait_ms", "d2h_ms", "replay_ms"):
+            avg[f] = sb[f]
     ranks = rank_split(job, sh, avg, split, elapsed / steps) if job.world > 1 else None
     return argparse.Namespace(res=res, step=step, elapsed=elapsed, st=st, avg=avg, ranks=ranks)
 
@@ -844,6 +871,17 @@ def drop_in(S, args, job, runner=None):
     return rec
 
 
+def dump_outputs(outdir, res):
+    """--dump-outputs: what the last timed step returned to its caller -- the
+    top-k hits, best first (at N > 1 rank 0's gathered global top-k) -- as
+    topk_scores.npy and topk_ids.npy, float64 (scores and IDs are far below
+    2^53, so exact); 2 k values in all."""
+    os.makedirs(outdir, exist_ok=True)
+    hits = list(res or [])
+    np.save(os.path.join(outdir, "topk_scores.npy"), np.array([h[0] for h in hits], dtype=np.float64))
+    np.save(os.path.join(outdir, "topk_ids.npy"), np.array([h[1] for h in hits], dtype=np.float64))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -900,8 +938,10 @@ def main():
     # --- the headline workload (BASELINE.json metric; default C2)
     w = workload(args, args.config)
     sh = load_shard(S, w, job)
-    t = timed_steps(S, job, sh, w, args.steps, args.warmup, args.k)
+    t = timed_steps(S, job, sh, w, args.steps, args.warmup, args.k, full=args.full)
     res, st = t.res, t.st
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     if args.timeline and world == 1:
         # untimed: every DP wave's start/end on the s_memrealtime clock
         S.set_option("timeline", 1)
@@ -910,23 +950,23 @@ def main():
         S.set_option("timeline", 0)
     S.free_sequence(sh.qq)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(sh.codes, sh.off, sh.q, matrix_table(w.matrix), w)
         except Exception as e:  # report, never hide
             cpu = {"value": None, "error": repr(e)}
-    match = fixture_match(w, sh, res, args.k, world)
+    match = fixture_match(w, sh, res, args.k, world) if args.full else None
     codes_off = (sh.codes, sh.off)
     sh.codes = sh.off = None
     del codes_off
 
-    # --- the north-star record (strong scaling of the fixed 10 M DB)
-    ns = None if args.no_north_star else north_star(S, args, job)
+    # --- the north-star record (strong scaling of the fixed 10 M DB; --full)
+    ns = north_star(S, args, job) if args.full and not args.no_north_star else None
     if job.native:
         S.dist_finalize()
-    # --- the drop-in record (N > 1: one process on all N devices)
+    # --- the drop-in record (--full, N > 1: one process on all N devices)
     di = None
-    if world > 1 and not args.no_drop_in:
+    if args.full and world > 1 and not args.no_drop_in:
         di = drop_in(S, args, job)
         if di is not None and ns is not None and ns.get("value") and di.get("value"):
             di["vs_multi_process"] = round(di["value"] / ns["value"], 4)
@@ -968,6 +1008,7 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 3),
+        "full": args.full,
         "higher_is_better": True,
         "scaling": "strong" if w.strong else "weak",
         "vs_baseline": None,
@@ -993,13 +1034,16 @@ def main():
                                  "frac": (cells_local / (kavg * 1e-3)) / valu_bound if valu_bound else None}},
         "kernel": {"name": st["kernel"], "avg_ms": round(kavg, 4),
                    "kernel_gcups": round(cells_local / (kavg * 1e-3) / 1e9, 2),
-                   "wide_ms_avg": round(t.avg["wide_ms"], 4), "wide_count": int(st["wide_count"]),
+                   **({"wide_ms_avg": round(t.avg["wide_ms"], 4)} if "wide_ms" in t.avg else {}),
+                   "wide_count": int(st["wide_count"]),
                    "valu_issue_bound_gcups": round(valu_bound / 1e9, 1) if valu_bound else None,
                    "valu_issue_frac": (cells_local / (kavg * 1e-3)) / valu_bound if valu_bound else None,
                    "valu_instr_per_cell": instr_per_cell},
-        "host_ms": {"search_call": round(t.avg["search_ms"], 3), "prep": round(t.avg["prep_ms"], 3),
-                    "upload": round(t.avg["upload_ms"], 3), "sync_wait": round(t.avg["sync_wait_ms"], 3),
-                    "d2h_filter": round(t.avg["d2h_ms"], 3), "replay": round(t.avg["replay_ms"], 3)},
+        # (search_call: the timed steps' own average; the breakdown is one more search's, --full)
+        "host_ms": {"search_call": round(t.avg["search_ms"], 3),
+                    **({"prep": round(t.avg["prep_ms"], 3), "upload": round(t.avg["upload_ms"], 3),
+                        "sync_wait": round(t.avg["sync_wait_ms"], 3), "d2h_filter": round(t.avg["d2h_ms"], 3),
+                        "replay": round(t.avg["replay_ms"], 3)} if "prep_ms" in t.avg else {})},
         "setup_s": round(sh.setup_s, 1),
         "setup": {"generate_and_write_fasta_s": round(sh.gen_s, 1), "init_db_and_pack_s": round(sh.load_s, 1),
                   "pack_ms": round(st["pack_ms"], 1)},
