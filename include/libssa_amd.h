@@ -84,8 +84,6 @@ typedef struct {
     int32_t slot_device[16];     /* per slot: its HIP device */
     double slot_kernel_ms[16];   /* per slot: HIP-event time of its DP kernels */
     double slot_search_ms[16];   /* per slot: host time of its device search and shard replay */
-    uint32_t graph;          /* slot 0's last search: 0 issued call by call, 1 captured into a new HIP graph,
-                                2 replayed the cached graph (option "graph") */
 } ssa_amd_stats_t;
 
 #define SSA_AMD_SW 0
@@ -144,11 +142,6 @@ void ssa_amd_get_stats( ssa_amd_stats_t * out );
  *   "filter_prefix_regs" 1|0  the top-k filter's block scan with its states in registers and
  *                        merges at the list width k needs, for DBs of <= 256 filter blocks
  *                        (default), or always the general scan
- *   "graph" 0|1          1: a single-view search with the device filter and no overflow counters runs
- *                        as cached HIP graphs -- the operations between its two timing records captured
- *                        once per launch plan, replayed with the changed kernel arguments set on their
- *                        nodes (stats graph); 0 (default: the graphs measured slower than the direct
- *                        calls): every stream operation issued on its own
  *   "upload_kernel" 1|0  1 (default): the per-search upload block (matrix, boundary, query) is read
  *                        from pinned host memory by a kernel on the search's stream; 0: a
  *                        copy-engine transfer (hipMemcpyAsync)
@@ -174,8 +167,6 @@ void ssa_amd_get_stats( ssa_amd_stats_t * out );
  *   "long16_rows" 1|0|2  queries beyond 1 024 rows: long16 passes planned by issue cost, up to 8
  *                        last rows scored by a row scan (default 1); 0: RL 16 passes; 2: the
  *                        cost model at every query length (q = 513: RL 8 + 1 scanned row)
- *   "pair_prio_groups" 0|-1|N  pair-kernel groups (longest first) at raised
- *                        wave priority: none (default), one per SIMD, N
  *   "timeline" 0|1       1: record every DP wave's start/end (ssa_amd_get_timeline)
  *   "pair_ticket" 1|0    pair-kernel workgroups take the next groups in start order
  *                        (an atomic ticket; default) or in blockIdx order
@@ -193,10 +184,6 @@ void ssa_amd_get_stats( ssa_amd_stats_t * out );
  *                        for three workgroups per CU, the rarest classes share one class scoring
  *                        the maximum of their rows, and the entries holding them that the device
  *                        filter forwards are re-scored exactly (stats rare_merged / rare_rescored)
- *   "filter_host" 0..3   the device filter's result through a D2H copy (0, default) or written by
- *                        the filter into pinned host memory (1: system-scope release, 2: system-
- *                        scope stores, the host spinning on a sequence word; 3: plain stores,
- *                        published by the end of the dispatch, the host synchronising as usual)
  *   "sync_spin" 1|0      1 (default): the host thread spins while a search runs (hipDeviceScheduleSpin,
  *                        set at the library's first pack on a device; 15 us less between two
  *                        searches); 0: HIP's own scheduling (yields the core).  The flag is
@@ -208,10 +195,6 @@ void ssa_amd_get_stats( ssa_amd_stats_t * out );
  *   "lean_events" 1|0    1 (default): no timing markers around the upload, the re-score tier
  *                        and the filter (stats upload_ms, wide_ms, d2h_ms read 0; kernel_ms
  *                        kept; C2 +0.5 %, profiles/r05/ab/lean_events); 0: all markers
- *   "side_tier" 0|1      1: the int32 re-score tier runs beside the device filter on a second
- *                        stream instead of in front of it (default 0: no gain measured)
- *   "pair_split" P       strip parts for every quad of groups (0, default) or only the first P %
- *                        (the longest, P > 0) or the last -P % (P < 0)
  *   "counters" -1|0|1    the reference's 8/16-bit overflow counters (stats overflow_8/16,
  *                        m_run's INFO line): -1 (default) only at output mode
  *                        OUTPUT_INFO, where the reference prints them; 0 never; 1 always

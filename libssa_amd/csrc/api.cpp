@@ -236,7 +236,6 @@ void publish_stats(const std::vector<SearchScores>& sc, const std::vector<SlotPl
     S.kernel_ms = S.wide_ms = S.d2h_ms = S.prep_ms = S.upload_ms = S.sync_wait_ms = 0;
     S.cells = S.entries = S.wide_count = S.kernel_bytes = S.filter_candidates = 0;
     S.slots = (uint32_t)std::min(sc.size(), (size_t)16);
-    S.graph = sc.empty() ? 0u : sc[0].graph;
     for (size_t i = 0; i < 16; i++) {
         S.slot_device[i] = i < S.slots ? plan[i].device : -1;
         S.slot_kernel_ms[i] = i < S.slots ? sc[i].kernel_ms : 0;
@@ -648,7 +647,6 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "long_waves")) cfg().long_waves = (int)value;
     else if (!strcmp(name, "long4_share_pct")) cfg().long4_share_pct = (int)value;
     else if (!strcmp(name, "long16")) cfg().long16 = (int)value;
-    else if (!strcmp(name, "pair_prio_groups")) cfg().pair_prio_groups = (int)value;
     else if (!strcmp(name, "timeline")) cfg().timeline = (int)value;
     else if (!strcmp(name, "pair_ticket")) cfg().pair_ticket = (int)value;
     else if (!strcmp(name, "pair_parts")) cfg().pair_parts = (int)value;
@@ -656,10 +654,7 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "counters")) cfg().counters = (int)value;
     else if (!strcmp(name, "part_wait_us")) cfg().part_wait_us = std::max(0L, value);
     else if (!strcmp(name, "rescore32")) cfg().rescore32 = (int)value;
-    else if (!strcmp(name, "filter_host")) cfg().filter_host = (int)value;
     else if (!strcmp(name, "rare_merge")) cfg().rare_merge = (int)value;
-    else if (!strcmp(name, "pair_split")) cfg().pair_split = (int)value;
-    else if (!strcmp(name, "side_tier")) cfg().side_tier = (int)value;
     else if (!strcmp(name, "sync_spin")) cfg().sync_spin = (int)value;
     else if (!strcmp(name, "lean_events")) cfg().lean_events = (int)value;
     else if (!strcmp(name, "long16_rows")) cfg().long16_rows = (int)value;
@@ -669,7 +664,6 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "tail_rows4")) cfg().tail_rows4 = (int)value;
     else if (!strcmp(name, "tier_defer")) cfg().tier_defer = (int)value;
     else if (!strcmp(name, "upload_kernel")) cfg().upload_kernel = (int)value;
-    else if (!strcmp(name, "graph")) cfg().graph = (int)value;
     else if (!strcmp(name, "plan_cache")) cfg().plan_cache = (int)value;
     else if (!strcmp(name, "long_latency")) cfg().long_latency = (int)value;
     else if (!strcmp(name, "filter_onepass")) cfg().filter_onepass = (int)value;

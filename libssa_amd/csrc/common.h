@@ -50,9 +50,6 @@ struct Config {
     int long4_share_pct = 1500;           // auto: 4 waves for groups longer than this % of a SIMD's share
                                           // (400 until round 6: NW's Swiss-Prot form +11 % at 1500, engine.cpp)
     int long16 = 1;                       // SW long entries on packed 16-bit patterns (long16_kernel) when exact
-    int graph = 0;                        // 1: the usual single-view search runs as cached HIP graphs (engine.cpp
-                                          // run_ops; measured slower than the direct calls on ROCm 7.2,
-                                          // profiles/r06/graph); 0 (default): every operation issued on its own
     int upload_kernel = 1;                // 1: the per-search upload block is read from pinned memory by a kernel
                                           // on the search's stream instead of a copy-engine transfer (-14 us
                                           // between searches, profiles/r05/host_gap/kgap_upk*.txt)
@@ -60,11 +57,11 @@ struct Config {
                                           // copy, only when the search has overflowed lanes
     int tail_rows4 = 1;                   // pair kernel tail strips at 4-row granularity (default heights)
     int long_prio = 1;                    // long16 waves at raised issue priority (s_setprio 3)
-    int long_pad = 1;
+    int long_pad = 1;                     // 1: long-entry workgroups pad their LDS to the pair kernel's (a finished
+                                          // one leaves exactly a pair workgroup's hole); 0: their own LDS only
     int filter_onepass = 1;               // kernels.hip filter_onepass (0: three launches)
     int long_latency = 1;                 // engine.cpp long_plan: a tiny DB's groups all go to the long kernels
-    int plan_cache = 1;                   // engine.cpp cached_plan (0: plan every search)                     // 1: long-entry workgroups pad their LDS to the pair kernel's (a finished
-                                          // one leaves exactly a pair workgroup's hole); 0: their own LDS only
+    int plan_cache = 1;                   // engine.cpp cached_plan (0: plan every search)
     int long_gate = 1;                    // the tables kernel holds the pair kernel until the long-entry
                                           // workgroups have started (TableArgs::gate)
     int long16_rows = 1;                  // long16_kernel may leave up to 8 query rows to its row scan (LongArgs::extra16)
@@ -78,30 +75,17 @@ struct Config {
     int timeline = 0;                     // record the DP waves' start/end (ssa_amd_get_timeline)
     int counters = -1;                    // the reference's 8/16-bit overflow counters: -1 auto (output mode
                                           // >= INFO, when m_run prints them), 0 never, 1 always
-    int pair_prio_groups = 0;             // pair_kernel groups at raised wave priority: -1 one per SIMD, 0 none (measured neutral)
     int sync_spin = 1;                    // 1: hipDeviceScheduleSpin for this library's devices (set at the first
                                           // pack on a device): the host spins, not yields, while a search runs
                                           // (-15 us between searches, profiles/r05/host_gap/kgap_spin.txt)
     int lean_events = 1;                  // 1 (default): no timing markers around the upload, the tier and the filter
                                           // (stats upload_ms / wide_ms / d2h_ms stay 0; kernel_ms kept;
                                           // C2 +0.5 %, profiles/r05/ab/lean_events)
-    int side_tier = 0;                    // 1: the int32 re-score tier runs beside the device filter (a second
-                                          // stream) instead of in front of it (single-view sparse searches;
-                                          // measured no gain, profiles/r05/ab/side_tier)
-    int pair_split = 0;                   // strip parts for all quads (0) or only the first P % (P > 0, the longest)
-                                          // or the last -P % (P < 0) of the quads
     int rare_merge = 0;                   // 1: when the query's residue classes leave the pair table too big for
                                           // three workgroups per CU, the rarest classes share one upper-bound
                                           // class and the forwarded entries holding them are re-scored exactly
                                           // (default off: Swiss-Prot form kernel +0.8 %, end to end -4 %,
                                           // profiles/r05/ab/merge_sprot2)
-    int filter_host = 0;                  // 1/2: the top-k filter writes its result into pinned host memory and
-                                          // the host spins on its sequence word (no D2H copy, no stream
-                                          // synchronisation; 1 with a system-scope release, 2 with system-
-                                          // scope stores and a store-completion wait); 3: the filter writes
-                                          // it with plain stores, the host synchronises with the stream (no
-                                          // copy); 0 (default: 1 and 2 measured slower,
-                                          // profiles/r05/ab/filter_host*): copy + hipStreamSynchronize
 };
 Config& cfg();
 // whether a search computes the overflow counters (Config::counters)

@@ -61,23 +61,10 @@ static void dfree(void* p) {
     if (p) (void)hipFree(p);
 }
 
-void DeviceDB::SearchGraph::reset() {
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (g) (void)hipGraphDestroy(g);
-    exec = nullptr;
-    g = nullptr;
-    ops.clear();
-    nodes.clear();
-    used = 0;
-}
-
 void DeviceDB::release() {
     // the buffers belong to `device`: free them there (a failure here means
     // the device is gone -- fatal, as every other HIP error of the library)
     if (device >= 0) check(hipSetDevice(device), "hipSetDevice");
-    // (the cached graph names the buffers freed below)
-    graph.reset();
-    graph.broken = false;
     plans.reset();
     dfree(d_groups); dfree(d_res); dfree(d_rowbuf); dfree(d_lane_len); dfree(d_lane_out);
     dfree(d_scores); dfree(d_ovf); dfree(d_wide); dfree(d_qpt); dfree(d_upblk);
@@ -453,7 +440,6 @@ void upload_pack(DeviceDB& D, HostPack& H, int dev) {
         // device-scope release, not a system-scope one (an L2 writeback of
         // the search's row-buffer lines each time, ~5 us on the path)
         for (auto& e : D.ev) check(hipEventCreateWithFlags(&e, kEventFlags), "hipEventCreate");
-        check(hipEventCreateWithFlags(&D.ev_fork, hipEventDisableTiming), "hipEventCreate");
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
             D.nsimd = (uint32_t)cus * 4;
@@ -1376,194 +1362,6 @@ static void ensure_entry_masks(DeviceDB& D) {
         for (; x; x &= x - 1) D.code_entries[__builtin_ctz(x)]++;
 }
 
-// ---------------------------------------------------------- search graph
-// A search's stream operations, recorded (launch.h), are replayed as one
-// HIP graph: the cached graph when the operations have the same shape as
-// the ones it was captured from (kinds, streams, kernels, grids, events,
-// argument sizes), with every changed argument block or copy set on its node
-// (hipGraphExecKernelNodeSetParams: the tables kernel's gate target, the pair
-// kernel's strip-part epoch, the candidate copy's length change per search);
-// otherwise the operations are captured into a new graph.  One graph launch
-// instead of ~12 calls: less host issue time and fewer barrier packets
-// between the kernels (tools/graph_probe.hip).
-static bool same_shape(const StreamOp& a, const StreamOp& b) {
-    if (a.kind != b.kind || a.stream != b.stream) return false;
-    switch (a.kind) {
-    case StreamOp::kKernel:
-        return a.func == b.func && a.grid.x == b.grid.x && a.grid.y == b.grid.y && a.grid.z == b.grid.z &&
-               a.block.x == b.block.x && a.block.y == b.block.y && a.block.z == b.block.z && a.lds == b.lds &&
-               a.args.size() == b.args.size() && a.arg_off == b.arg_off;
-    case StreamOp::kCopy:
-        return a.ck == b.ck;
-    case StreamOp::kSet:
-        return a.dst == b.dst && a.value == b.value && a.bytes == b.bytes;
-    case StreamOp::kRecord:
-        return a.event == b.event && a.timing == b.timing;
-    case StreamOp::kWait:
-        return a.event == b.event;
-    }
-    return false;
-}
-
-static void issue_all(const std::vector<StreamOp>& ops) {
-    for (const StreamOp& op : ops) check(issue_op(op, false), "stream operation");
-}
-
-// A sync point inside the recording window: what was recorded is issued as
-// it stands and the rest of the search runs call by call.
-static void sync_point(hipStream_t s, const char* what) {
-    if (OpRecorder* r = op_recorder()) {
-        if (trace_on()) fprintf(stderr, "trace: search graph: sync point (%s) after %zu ops\n", what, r->ops.size());
-        op_recorder() = nullptr;
-        issue_all(r->ops);
-        r->ops.clear();
-    }
-    check(hipStreamSynchronize(s), what);
-}
-
-static bool capture_ops(DeviceDB::SearchGraph& G, const std::vector<StreamOp>& ops, hipStream_t st) {
-    G.reset();
-    auto fail = [&](const char* what, size_t i, hipError_t e) {
-        if (trace_on())
-            fprintf(stderr, "trace: search graph: %s failed at op %zu of %zu (kind %d): %s\n", what, i, ops.size(),
-                    i < ops.size() ? (int)ops[i].kind : -1, hipGetErrorString(e));
-        return false;
-    };
-    hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return fail("begin capture", 0, e);
-    std::vector<hipGraphNode_t> nodes(ops.size(), nullptr);
-    bool ok = true;
-    for (size_t i = 0; i < ops.size() && ok; i++) {
-        const StreamOp& op = ops[i];
-        e = issue_op(op, true);
-        ok = e == hipSuccess || fail("capture", i, e);
-        if (ok && (op.kind == StreamOp::kKernel || op.kind == StreamOp::kCopy || op.kind == StreamOp::kSet)) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            const hipGraphNode_t* deps = nullptr;
-            size_t nd = 0;
-            e = hipStreamGetCaptureInfo_v2(op.stream, &cs, nullptr, nullptr, &deps, &nd);
-            ok = (e == hipSuccess && cs == hipStreamCaptureStatusActive && nd == 1 && deps) ||
-                 fail(e != hipSuccess ? "capture info" : cs != hipStreamCaptureStatusActive ? "capture status"
-                                                                                             : "node count", i, e);
-            if (ok) nodes[i] = deps[0];
-        }
-    }
-    hipGraph_t g = nullptr;
-    e = hipStreamEndCapture(st, &g);
-    if (ok && (e != hipSuccess || !g)) ok = fail("end capture", ops.size(), e);
-    if (ok) {
-        e = hipGraphInstantiate(&G.exec, g, nullptr, nullptr, 0);
-        if (e != hipSuccess) ok = fail("instantiate", ops.size(), e);
-    }
-    if (!ok) {
-        if (g) (void)hipGraphDestroy(g);
-        G.exec = nullptr;
-        (void)hipGetLastError();
-        return false;
-    }
-    G.g = g;
-    G.ops = ops;
-    G.nodes = std::move(nodes);
-    return true;
-}
-
-// One segment of a search's operations (no timing record inside) as a
-// cached graph.  Returns 0: issued call by call, 1: captured, 2: replayed.
-static uint32_t run_segment(DeviceDB& D, const std::vector<StreamOp>& ops, hipStream_t st) {
-    auto shape_of = [&](const DeviceDB::SearchGraph& x) {
-        bool same = x.exec && x.ops.size() == ops.size();
-        for (size_t i = 0; same && i < ops.size(); i++) same = same_shape(x.ops[i], ops[i]);
-        return same;
-    };
-    DeviceDB::SearchGraph* pg = nullptr;
-    for (auto& x : D.graph.slot)
-        if (shape_of(x)) pg = &x;
-    bool same = pg != nullptr;
-    if (!pg) {
-        // a free slot, else the least recently used
-        for (auto& x : D.graph.slot)
-            if (!x.exec) {
-                pg = &x;
-                break;
-            }
-        if (!pg) {
-            pg = &D.graph.slot[0];
-            for (auto& x : D.graph.slot)
-                if (x.used < pg->used) pg = &x;
-        }
-    }
-    DeviceDB::SearchGraph& G = *pg;
-    const double t0 = now_ms();
-    uint32_t nset = 0;
-    if (same) {
-        for (size_t i = 0; same && i < ops.size(); i++) {
-            const StreamOp &a = ops[i], &b = G.ops[i];
-            if (a.kind == StreamOp::kKernel && a.args != b.args) {
-                void* p[32];
-                for (size_t j = 0; j < a.arg_off.size() && j < 32; j++) p[j] = (void*)(a.args.data() + a.arg_off[j]);
-                hipKernelNodeParams kp{};
-                kp.blockDim = a.block;
-                kp.gridDim = a.grid;
-                kp.func = const_cast<void*>(a.func);
-                kp.kernelParams = p;
-                kp.sharedMemBytes = a.lds;
-                same = hipGraphExecKernelNodeSetParams(G.exec, G.nodes[i], &kp) == hipSuccess;
-                nset++;
-            } else if (a.kind == StreamOp::kCopy && (a.dst != b.dst || a.src != b.src || a.bytes != b.bytes)) {
-                same = hipGraphExecMemcpyNodeSetParams1D(G.exec, G.nodes[i], a.dst, a.src, a.bytes, a.ck) == hipSuccess;
-            }
-        }
-        if (same) G.ops = ops;
-        else (void)hipGetLastError();
-    }
-    if (!same && !capture_ops(G, ops, st)) {
-        // (this device searches call by call from now on)
-        D.graph.reset();
-        D.graph.broken = true;
-        if (trace_on()) fprintf(stderr, "trace: search graph capture failed; direct launches\n");
-        issue_all(ops);
-        return 0;
-    }
-    G.used = ++D.graph.clock;
-    const double t1 = now_ms();
-    check(hipGraphLaunch(G.exec, st), "graph launch");
-    if (trace_on())
-        fprintf(stderr, "trace: search graph: segment of %zu ops, %s, %u kernel arguments set, %.1f us, launch %.1f us\n",
-                ops.size(), same ? "replayed" : "captured", nset, (t1 - t0) * 1e3, (now_ms() - t1) * 1e3);
-    return same ? 2u : 1u;
-}
-
-// A recorded search: its timing records (kernel_ms: after the upload, after
-// the DP kernels' join) are issued on the stream as they are -- their
-// timestamps then mark exactly what they mark in a direct search -- and the
-// operations between them run as cached graphs (a lone operation directly).
-// Returns 0: issued call by call, 1: some segment captured, 2: all replayed.
-static uint32_t run_ops(DeviceDB& D, OpRecorder& rec, hipStream_t st) {
-    const std::vector<StreamOp>& ops = rec.ops;
-    if (ops.empty()) return 0;
-    uint32_t mode = 2;
-    bool any = false;
-    size_t i = 0;
-    while (i < ops.size()) {
-        if (ops[i].kind == StreamOp::kRecord && ops[i].timing) {
-            check(issue_op(ops[i], false), "event");
-            i++;
-            continue;
-        }
-        size_t j = i;
-        while (j < ops.size() && !(ops[j].kind == StreamOp::kRecord && ops[j].timing)) j++;
-        if (j - i == 1 || D.graph.broken) {
-            for (size_t x = i; x < j; x++) check(issue_op(ops[x], false), "stream operation");
-        } else {
-            const std::vector<StreamOp> seg(ops.begin() + i, ops.begin() + j);
-            mode = std::min(mode, run_segment(D, seg, st));
-            any = true;
-        }
-        i = j;
-    }
-    return any ? mode : 0u;
-}
-
 bool batch_pipelinable(size_t nqueries, size_t k) {
     return nqueries > 1 && k > 0 && k <= (size_t)kFilterMaxK && !cfg().no_filter;
 }
@@ -1622,11 +1420,11 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     // the counters are zeroed only when this search computes them)
     if (E > 0) {
         if (D.cnt_dirty) {
-            check(op_set(D.d_cnt, 0, 16 * kMaxBatchPipe + 16, D.stream), "memset");
+            check(hipMemsetAsync(D.d_cnt, 0, 16 * kMaxBatchPipe + 16, D.stream), "memset");
             D.gate_count = 0;
             D.cnt_dirty = false;
         } else if (want_counts) {
-            check(op_set(D.d_cnt, 0, 16 * kMaxBatchPipe, D.stream), "memset");
+            check(hipMemsetAsync(D.d_cnt, 0, 16 * kMaxBatchPipe, D.stream), "memset");
         }
     }
     const uint32_t gate0 = D.gate_count;
@@ -1652,18 +1450,9 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     const bool multi = out.sparse && V > 1 && !ind;
     const bool piped = multi || ind;
     const bool lean = C.lean_events != 0;   // (option "lean_events": no upload/tier/filter markers)
-    // the sparse single-pass filter hands its result straight to the host
-    // (FilterArgs::host_out) unless something else still has to be copied
-    // back on the stream (the overflow counters)
-    bool host_direct = C.filter_host && out.sparse && !ind && !want_counts;
     // the rare-code merge (plan_view) needs the single-pass filter and no
     // counters (they decide from exact scores)
     const bool allow_merge = C.rare_merge && V == 1 && !ind && out.sparse && !want_counts && E > 0;
-    // option "graph": the usual search -- one query view, the device filter,
-    // no counters, the result copied back -- runs as a cached HIP graph
-    const bool use_graph = C.graph && !D.graph.broken && V == 1 && out.sparse && !ind && !want_counts &&
-                           !host_direct && !C.timeline && !C.side_tier && !allow_merge;
-    OpRecorder rec;
     if (allow_merge && D.alpha > 21) ensure_entry_masks(D);
     // every lane fits a view's overflow list (reference: no limit on the
     // sequences search_16.c:101-109 re-runs at 64 bits)
@@ -1850,7 +1639,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             // the reference skips the pair (no overflow)
             for (size_t e = 0; e < E; e++)
                 hs[e] = nw ? (int32_t)(Q + (int64_t)D.meta.len[e] * R) : 0;
-            if (want_counts) check(op_set(D.d_flags + v * E, 0, E, D.stream), "memset");
+            if (want_counts) check(hipMemsetAsync(D.d_flags + v * E, 0, E, D.stream), "memset");
             continue;
         }
         // which kernels, bounds and strip plan (plan_view); a fused batch
@@ -1862,7 +1651,6 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
         const ViewPlan& vp = vpl;
         const bool merge = vp.merge_mask != 0;
         if (merge) {
-            host_direct = false;           // (the exact re-score follows the filter)
             // lanes, then int64 scores, for every entry that holds a merged code
             const size_t cap = std::max<uint64_t>(vp.merge_entries, 1);
             if (D.exact_cap < cap) {
@@ -2051,20 +1839,14 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 memcpy(up_m + qm_off + 4 * i, &mi, 4);
             }
         if (!qpt.empty()) memcpy(up_q, qpt.data(), qpt.size() * 4);
-        // a graph-eligible search records its stream operations from here to
-        // the result's copy and replays them as one HIP graph (run_ops)
-        if (use_graph) {
-            rec.ops.clear();
-            op_recorder() = &rec;
-        }
-        if (!lean) check(op_record(D.ev[4], st, true), "event");
+        if (!lean) check(hipEventRecord(D.ev[4], st), "event");
         if (!qpt.empty())
-            check(op_copy(dqpt, up_q, qpt.size() * 4, hipMemcpyHostToDevice, st), "H2D qpt");
+            check(hipMemcpyAsync(dqpt, up_q, qpt.size() * 4, hipMemcpyHostToDevice, st), "H2D qpt");
         if (C.upload_kernel)
             check(launch_upload(dup, up_m, (blk_bytes + 3) & ~(size_t)3, st), "upload kernel");
         else
-            check(op_copy(dup, up_m, blk_bytes, hipMemcpyHostToDevice, st), "H2D uploads");
-        if (piped) check(op_record(D.ev[5], st), "event");   // staging buffer free again
+            check(hipMemcpyAsync(dup, up_m, blk_bytes, hipMemcpyHostToDevice, st), "H2D uploads");
+        if (piped) check(hipEventRecord(D.ev[5], st), "event");   // staging buffer free again
         // overflow list of this view: the whole list, or in a multi-view
         // search its own slice (all views stay on the device until the end)
         uint32_t* ovf = D.d_ovf + (piped ? v * (ovf_capv + 1) : 0);
@@ -2117,23 +1899,14 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
 
         // the int32 re-score tier for this view's overflowed lanes, when exact
         const int rl32 = rescore32_rl(D, m, A, Q, R, minM, maxM);
-        // the int32 tier beside the filter (on stream_long1, after the DP
-        // kernels) instead of in front of it: the filter does not read its
-        // output, so the tier leaves the path from the pair kernel's end to
-        // the result; the tables kernel then clears the filter header
-        const bool side_tier = C.side_tier && rl32 > 0 && use_pair && out.sparse && !piped && !want_counts;
-        // (the host then waits for the stream's end, which covers the tier:
-        // a filter result handed straight to pinned memory would let the
-        // host read d_wide, and the tier's end event, before the tier ran)
-        if (side_tier) host_direct = false;
-        // ... or after it, only when the search has overflowed lanes: the
-        // filter forwards every overflowed lane (INT32_MIN) and leaves it out
-        // of its bounds, so the tier's exact scores are needed only by the
-        // host, which sees the list's length in the candidate header -- the
-        // usual search (no overflow) then skips the tier's launch (~5 us on
-        // the path from the pair kernel to the result, profiles/r05/host_gap)
-        const bool defer_tier = C.tier_defer && !side_tier && rl32 > 0 && use_pair && out.sparse && !piped &&
-                                !want_counts && !merge;
+        // the tier after the filter instead of in front of it, only when the
+        // search has overflowed lanes: the filter forwards every overflowed
+        // lane (INT32_MIN) and leaves it out of its bounds, so the tier's
+        // exact scores are needed only by the host, which sees the list's
+        // length in the candidate header -- the usual search (no overflow)
+        // then skips the tier's launch (~5 us on the path from the pair
+        // kernel to the result, profiles/r05/host_gap)
+        const bool defer_tier = C.tier_defer && rl32 > 0 && use_pair && out.sparse && !piped && !want_counts && !merge;
         LongArgs ra{};
         if (rl32 > 0) {
             ra.res = dres;
@@ -2160,7 +1933,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 ra.stride = D.group_ncols[0] + 16;
                 const size_t need = (size_t)ra.blocks * kLongWaves * ra.stride;
                 if (D.rscratch_cap < need) {
-                    if (piped && v > 0) sync_point(D.stream, "sync");
+                    if (piped && v > 0) check(hipStreamSynchronize(D.stream), "sync");
                     dfree(D.d_rscratch);
                     check(hipMalloc((void**)&D.d_rscratch, need * 8), "re-score scratch");
                     D.rscratch_cap = need;
@@ -2185,19 +1958,11 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 check(hipMalloc((void**)&D.d_timeline, rows * sizeof(uint4)), "timeline");
                 D.timeline_cap = rows;
             }
-            check(op_set(D.d_timeline, 0, rows * sizeof(uint4), st), "memset");
+            check(hipMemsetAsync(D.d_timeline, 0, rows * sizeof(uint4), st), "memset");
             D.timeline_rows = rows;
             tl = D.d_timeline;
         }
-        check(op_record(ev_k0, st, true), "event");
-        // the long-entry streams fork here: in a recorded search through an
-        // event of its own, recorded inside the graph segment that follows
-        // (ev_k0 is issued on the stream between two graphs, run_ops)
-        hipEvent_t fork_ev = ev_k0;
-        if (op_recorder()) {
-            fork_ev = D.ev_fork;
-            check(op_record(fork_ev, st), "event");
-        }
+        check(hipEventRecord(ev_k0, st), "event");   // (the long-entry streams fork here)
         std::vector<std::function<void()>> long_launch;   // the long-entry kernels' launches
         uint32_t long4 = 0;        // leading groups at 4 waves per entry, the rest of long_groups at 1
         bool long_hmm = false;     // long_kernel wrote the NW extremes (D.d_hmm)
@@ -2262,9 +2027,9 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             }
             if (need_hmm) {
                 if (D.hmm_cap < (size_t)long_groups * 64) {
-                    sync_point(D.stream_long, "sync");
-                    sync_point(D.stream_long1, "sync");
-                    if (piped && v > 0) sync_point(st, "sync");
+                    check(hipStreamSynchronize(D.stream_long), "sync");
+                    check(hipStreamSynchronize(D.stream_long1), "sync");
+                    if (piped && v > 0) check(hipStreamSynchronize(st), "sync");
                     dfree(D.d_hmm);
                     check(hipMalloc((void**)&D.d_hmm, (size_t)long_groups * 64 * sizeof(int2)), "long-entry extremes");
                     D.hmm_cap = (size_t)long_groups * 64;
@@ -2281,8 +2046,8 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 la.stride = D.group_ncols[0] + 16;
                 const size_t need = (size_t)long_groups * 64 * la.stride;
                 if (D.lscratch_cap < need) {
-                    sync_point(D.stream_long, "sync");
-                    sync_point(D.stream_long1, "sync");
+                    check(hipStreamSynchronize(D.stream_long), "sync");
+                    check(hipStreamSynchronize(D.stream_long1), "sync");
                     dfree(D.d_lscratch);
                     check(hipMalloc((void**)&D.d_lscratch, need * 8), "long-entry scratch");
                     D.lscratch_cap = need;
@@ -2310,9 +2075,9 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                         check(launch_long(la, 4, rl4, nw, st), "long kernel launch");
                         return;
                     }
-                    check(op_wait(D.stream_long, fork_ev), "event wait");
+                    check(hipStreamWaitEvent(D.stream_long, ev_k0, 0), "event wait");
                     check(launch_long(la, 4, rl4, nw, D.stream_long), "long kernel launch");
-                    check(op_record(D.ev[7], D.stream_long), "event");
+                    check(hipEventRecord(D.ev[7], D.stream_long), "event");
                 });
             }
             if (long4 < long_groups) {
@@ -2328,10 +2093,10 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 }
                 long_launch.push_back([=, &D]() {
                     const hipStream_t ls = long_only ? st : D.stream_long1;
-                    if (!long_only) check(op_wait(ls, fork_ev), "event wait");
+                    if (!long_only) check(hipStreamWaitEvent(ls, ev_k0, 0), "event wait");
                     if (rl16 > 0) check(launch_long16(la, rl16, ls), "long kernel launch");
                     else check(launch_long(la, 1, rl1, nw, ls), "long kernel launch");
-                    if (!long_only) check(op_record(D.ev[6], ls), "event");
+                    if (!long_only) check(hipEventRecord(D.ev[6], ls), "event");
                 });
             }
             if (v == 0) {
@@ -2365,7 +2130,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             ta.rel = rel;
             ta.pad = (uint32_t)(uint16_t)padv;
             ta.zero = ovf;
-            if (side_tier || defer_tier) {
+            if (defer_tier) {
                 ta.zero_hdr = D.d_fbuf;
                 ta.nzero_hdr = kFilterHeader;
             }
@@ -2395,7 +2160,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             }
             check(launch_pair_tables(ta, st), "pair tables kernel");
         } else {
-            check(op_set(ovf, 0, 4, st), "memset");
+            check(hipMemsetAsync(ovf, 0, 4, st), "memset");
         }
         for (auto& f : long_launch) f();
 
@@ -2407,14 +2172,9 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             b.g_first = long_groups;
             if (C.pair_ticket) b.ticket = gate + 1;    // zeroed by the tables kernel just before
             b.timeline = tl ? tl + (size_t)long_groups * 64 : nullptr;
-            // the first wave on every SIMD holds one of the longest groups; it
-            // shares the SIMD with two other waves, so at equal priority it
-            // runs at a third of the issue rate and, on a DB that fills the chip
-            // only a few times over, outlasts the rest of the launch
-            {
-                const uint32_t pg = C.pair_prio_groups < 0 ? D.nsimd : (uint32_t)C.pair_prio_groups;
-                b.g_prio = (uint32_t)std::min<uint64_t>((uint64_t)long_groups + pg, D.ngroups);
-            }
+            // (no group at raised wave priority: g_prio = g_first; a dead
+            // kernel input, DESIGN.md §7 "built, measured, removed")
+            b.g_prio = std::min<uint32_t>(long_groups, D.ngroups);
             // a fused batch: view 0's arguments plus per-query strides cover
             // every view, launched once after the last view's tables
             if (fused && v == 0) {
@@ -2444,7 +2204,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 if (parts > 2 && !D.d_rowbuf3 && D.ngroups > long_groups) {
                     // the third part's row buffer (4 B per residue slot); without
                     // the memory for it the search runs two parts
-                    if (piped && v > 0) sync_point(st, "sync");
+                    if (piped && v > 0) check(hipStreamSynchronize(st), "sync");
                     if (hipMalloc((void**)&D.d_rowbuf3, (size_t)D.nblocks * 4096) != hipSuccess) {
                         (void)hipGetLastError();
                         D.d_rowbuf3 = nullptr;
@@ -2456,11 +2216,11 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     const uint32_t ps = (T + parts - 1) / parts;
                     parts = (T + ps - 1) / ps;
                     if (D.part_cap < quads * nqf || D.smax_cap < (size_t)D.ngroups * 64 * nqf) {
-                        if (piped && v > 0) sync_point(st, "sync");
+                        if (piped && v > 0) check(hipStreamSynchronize(st), "sync");
                         if (D.part_cap < quads * nqf) {
                             dfree(D.d_part);
                             check(hipMalloc((void**)&D.d_part, (size_t)quads * nqf * 4), "strip parts");
-                            check(op_set(D.d_part, 0, (size_t)quads * nqf * 4, st), "memset");
+                            check(hipMemsetAsync(D.d_part, 0, (size_t)quads * nqf * 4, st), "memset");
                             D.part_cap = quads * nqf;
                         }
                         if (D.smax_cap < (size_t)D.ngroups * 64 * nqf) {
@@ -2479,14 +2239,8 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     b.nparts = parts;
                     b.part_strips = ps;
                     b.nquads = quads;
-                    // option pair_split: only the first P % of the quads (the
-                    // longest, P > 0) or the last -P % (P < 0) are split
-                    b.split_q0 = 0;
+                    b.split_q0 = 0;            // (every quad is split)
                     b.split_q1 = quads;
-                    if (C.pair_split > 0 && C.pair_split < 100)
-                        b.split_q1 = std::max<uint32_t>(1, (uint32_t)((uint64_t)quads * C.pair_split / 100));
-                    else if (C.pair_split < 0 && C.pair_split > -100)
-                        b.split_q0 = quads - std::max<uint32_t>(1, (uint32_t)((uint64_t)quads * -C.pair_split / 100));
                     b.part_done = D.d_part;
                     b.part_smax = D.d_smax;
                     b.part_err = gate + 2;
@@ -2499,7 +2253,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                         b.rowbuf2 = (uint4*)(D.d_rowbuf_q + nqf * (size_t)D.nblocks * 4096);
                     } else {
                         if (!D.d_rowbuf2) {
-                            if (piped && v > 0) sync_point(st, "sync");
+                            if (piped && v > 0) check(hipStreamSynchronize(st), "sync");
                             check(hipMalloc((void**)&D.d_rowbuf2, (size_t)D.nblocks * 4096), "second row buffer");
                         }
                         b.rowbuf2 = D.d_rowbuf2;
@@ -2555,7 +2309,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             }
             // a fused batch's DP time runs from this one launch (not from view
             // 0's start: the host prepared the other views in between)
-            if (fused && v + 1 == V) check(op_record(D.vev[2 * V], st, true), "event");
+            if (fused && v + 1 == V) check(hipEventRecord(D.vev[2 * V], st), "event");
             if (!fused || v + 1 == V) {
                 check(launch_pair(b, pnp, tail_np, nw, (size_t)pair_lds_rows(A) * (lnp + 4) * 4, st), "pair kernel launch");
                 host_mark("pair issued");
@@ -2567,15 +2321,10 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
         // overflow flags, its filter pass (a fused batch defers it until the
         // one pair launch that covers every view)
         auto post = [=, &D, &kernel_bytes, &counted]() {
-            if (long4 > 0 && !long_only) check(op_wait(st, D.ev[7]), "event wait");
-            if (long4 < long_groups && !long_only) check(op_wait(st, D.ev[6]), "event wait");
-            check(op_record(ev_k1, st, true), "event");
-            if (side_tier) {
-                // (header cleared by the tables kernel; no counters)
-                check(op_wait(D.stream_long1, ev_k1), "event wait");
-                check(launch_long(ra, 1, rl32, nw, D.stream_long1), "int32 re-score launch");
-                check(op_record(D.ev[8], D.stream_long1), "event");
-            } else if (defer_tier) {
+            if (long4 > 0 && !long_only) check(hipStreamWaitEvent(st, D.ev[7], 0), "event wait");
+            if (long4 < long_groups && !long_only) check(hipStreamWaitEvent(st, D.ev[6], 0), "event wait");
+            check(hipEventRecord(ev_k1, st), "event");
+            if (defer_tier) {
                 // (after the result's copy, if the header reports overflowed lanes)
             } else if (rl32 > 0) {
                 // the int32 tier clears what wide_kernel would have (one launch)
@@ -2650,7 +2399,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     fa.rthreads = (uint32_t)std::max<size_t>(64, std::min<size_t>(1024, (64ull << 20) / (8ull * fa.rstride)) / 64 * 64);
                     const size_t need = (size_t)fa.rthreads * 2 * fa.rstride;
                     if (D.frwork_cap < need) {
-                        if (piped && v > 0) sync_point(st, "sync");
+                        if (piped && v > 0) check(hipStreamSynchronize(st), "sync");
                         dfree(D.d_frwork);
                         check(hipMalloc((void**)&D.d_frwork, need * 4), "row-major replay scratch");
                         D.frwork_cap = need;
@@ -2670,7 +2419,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     check(launch_count(ca, st), "overflow count launch");
                 }
                 if (v + 1 == V) {
-                    check(op_copy(D.h_cnt, D.d_cnt, 16 * (ind ? V : 1), hipMemcpyDeviceToHost, st), "D2H counters");
+                    check(hipMemcpyAsync(D.h_cnt, D.d_cnt, 16 * (ind ? V : 1), hipMemcpyDeviceToHost, st), "D2H counters");
                     counted = true;
                 }
             }
@@ -2696,7 +2445,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 f.cand = (uint2*)(reg + kFilterHeader);
                 one_pass(f);
                 check(launch_filter(f, st), "filter launch");
-                check(op_copy((uint8_t*)D.h_fbuf + v * hreg, reg, kFilterHeader * 4 + 8 * std::min(D.h_cand_cap, E),
+                check(hipMemcpyAsync((uint8_t*)D.h_fbuf + v * hreg, reg, kFilterHeader * 4 + 8 * std::min(D.h_cand_cap, E),
                                      hipMemcpyDeviceToHost, st), "D2H candidates");
             }
         };
@@ -2732,12 +2481,12 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             one_pass(f);
             check(launch_filter(f, st), "filter launch");
             for (size_t vv = 0; vv < V; vv++)
-                check(op_copy((uint8_t*)D.h_fbuf + vv * hreg, (uint8_t*)D.d_fbuf + vv * dreg,
+                check(hipMemcpyAsync((uint8_t*)D.h_fbuf + vv * hreg, (uint8_t*)D.d_fbuf + vv * dreg,
                                      kFilterHeader * 4 + 8 * std::min(D.h_cand_cap, E), hipMemcpyDeviceToHost, st),
                       "D2H candidates");
         }
         if (piped && v + 1 < V) continue;
-        if (!lean) check(op_record(D.ev[2], st, true), "event");
+        if (!lean) check(hipEventRecord(D.ev[2], st), "event");
         if (ind) {
             // (filters already enqueued per query)
         } else if (out.sparse) {
@@ -2757,17 +2506,10 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             f.counters = D.d_fbuf;
             f.status = gate + 2;
             f.cand = (uint2*)(D.d_fbuf + kFilterHeader);
-            if (host_direct) {
-                // the filter writes header + first candidates into h_fbuf and
-                // then the sequence word the host spins on below
-                if (++D.filter_seq == 0) D.filter_seq = 1;
-                __atomic_store_n(&D.h_fbuf[kFilterSeqWord], 0u, __ATOMIC_RELEASE);
-                f.host_out = D.h_fbuf;
-                f.host_cap = (uint32_t)std::min<size_t>(D.h_cand_cap, f.n);
-                f.host_seq = D.filter_seq;
-                f.done = gate + 3;
-                f.host_fence = C.filter_host == 1 ? 1u : C.filter_host == 3 ? 2u : 0u;
-            }
+            // (the result comes back through the copy below: the filter's own
+            // write to host memory is a dead kernel input)
+            f.host_out = nullptr;
+            f.host_fence = 0;
             const size_t xcap_al = (D.exact_cap + 1) & ~(size_t)1;     // (int64 scores 8-byte aligned)
             if (merge) {
                 f.emask = D.d_emask;
@@ -2778,8 +2520,6 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             }
             one_pass(f);
             check(launch_filter(f, st), "filter launch");
-            // (the stream's end, and so the host's wake-up, covers the tier)
-            if (side_tier) check(op_wait(st, D.ev[8]), "event wait");
             if (merge) {
                 // the forwarded merged-code entries, exactly: the int32 tier
                 // over their lanes (count: the filter header's word 1) on the
@@ -2804,7 +2544,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     xa.stride = D.group_ncols[0] + 16;
                     const size_t need = (size_t)xa.blocks * kLongWaves * xa.stride;
                     if (D.rscratch_cap < need) {
-                        sync_point(st, "sync");
+                        check(hipStreamSynchronize(st), "sync");
                         dfree(D.d_rscratch);
                         check(hipMalloc((void**)&D.d_rscratch, need * 8), "re-score scratch");
                         D.rscratch_cap = need;
@@ -2813,68 +2553,36 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 }
                 check(launch_long(xa, 1, vp.merge_rl, nw, st), "exact re-score launch");
                 const size_t nx = std::min(kExactPinned, D.exact_cap);
-                check(op_copy(D.h_exact, D.d_exact, nx * 4, hipMemcpyDeviceToHost, st), "D2H exact lanes");
-                check(op_copy(D.h_exact + kExactPinned * 4, D.d_exact + xcap_al, nx * 8, hipMemcpyDeviceToHost, st),
+                check(hipMemcpyAsync(D.h_exact, D.d_exact, nx * 4, hipMemcpyDeviceToHost, st), "D2H exact lanes");
+                check(hipMemcpyAsync(D.h_exact + kExactPinned * 4, D.d_exact + xcap_al, nx * 8, hipMemcpyDeviceToHost, st),
                       "D2H exact scores");
             }
-            if (!host_direct) {
-                // one copy: counters (incl. the overflow counts) + the first
-                // candidates -- twice the last search's count, at least 256
-                // (a short copy is most of a copy's latency; more candidates
-                // than that come in a second copy after the synchronisation)
-                const size_t first = std::min<size_t>(std::min<size_t>(D.h_cand_cap, f.n),
-                                                      std::max<size_t>(256, 2 * (size_t)D.cand_hint + 64));
-                D.cand_first = first;
-                check(op_copy(D.h_fbuf, D.d_fbuf, kFilterHeader * 4 + 8 * first, hipMemcpyDeviceToHost, st),
-                      "D2H candidates");
-            }
+            // one copy: counters (incl. the overflow counts) + the first
+            // candidates -- twice the last search's count, at least 256
+            // (a short copy is most of a copy's latency; more candidates
+            // than that come in a second copy after the synchronisation)
+            const size_t first = std::min<size_t>(std::min<size_t>(D.h_cand_cap, f.n),
+                                                  std::max<size_t>(256, 2 * (size_t)D.cand_hint + 64));
+            D.cand_first = first;
+            check(hipMemcpyAsync(D.h_fbuf, D.d_fbuf, kFilterHeader * 4 + 8 * first, hipMemcpyDeviceToHost, st),
+                  "D2H candidates");
         } else {
-            check(op_copy(hs, D.d_scores, E * 4, hipMemcpyDeviceToHost, st), "D2H scores");
+            check(hipMemcpyAsync(hs, D.d_scores, E * 4, hipMemcpyDeviceToHost, st), "D2H scores");
             // (the first kOvfPinned entries; d_ovf holds ovf_capv + 1 dwords)
             const size_t pre = std::min(kOvfPinned, ovf_capv);
-            check(op_copy(D.h_ovf, D.d_ovf, 4 * (pre + 1), hipMemcpyDeviceToHost, st), "D2H overflow");
-            check(op_copy(D.h_wide, D.d_wide, 8 * pre, hipMemcpyDeviceToHost, st), "D2H wide");
+            check(hipMemcpyAsync(D.h_ovf, D.d_ovf, 4 * (pre + 1), hipMemcpyDeviceToHost, st), "D2H overflow");
+            check(hipMemcpyAsync(D.h_wide, D.d_wide, 8 * pre, hipMemcpyDeviceToHost, st), "D2H wide");
         }
         // the strip-part wait status: the filter passes copy it into their
         // candidate headers (word 2); only a search without them reads it back
         uint32_t* const h_perr = (uint32_t*)(D.h_cnt + 2 * kMaxBatchPipe) + 2;
         const bool perr_in_header = ind || out.sparse;
         if (parts_used && !perr_in_header)
-            check(op_copy(h_perr, gate + 2, 4, hipMemcpyDeviceToHost, st), "D2H part status");
-        out.graph = 0;
-        if (op_recorder()) {
-            op_recorder() = nullptr;
-            out.graph = run_ops(D, rec, st);
-        }
-        if (trace_on()) fprintf(stderr, "trace: search graph: eligible %d, ops %zu, mode %u\n", (int)use_graph, rec.ops.size(), out.graph);
+            check(hipMemcpyAsync(h_perr, gate + 2, 4, hipMemcpyDeviceToHost, st), "D2H part status");
         const double t_sync0 = now_ms();
         host_mark("issued");
-        // filter_host 3: the filter's own stores, made visible by the end of
-        // its dispatch -- an ordinary synchronisation, no copy, no spin
-        const bool spin = host_direct && C.filter_host != 3;
-        if (spin) {
-            // spin on the filter's sequence word in pinned memory: the result is
-            // here as soon as the last filter block has written it, before the
-            // kernel's end-of-dispatch cache writeback and completion signal
-            // (the stream keeps that tail; the next search queues behind it).
-            // A drained stream without the word is a library bug: fatal.
-            const volatile uint32_t* seqw = D.h_fbuf + kFilterSeqWord;
-            for (uint64_t it = 1; __atomic_load_n(seqw, __ATOMIC_ACQUIRE) != D.filter_seq; it++) {
-                if ((it & 1023) == 0) {
-                    const hipError_t q = hipStreamQuery(st);
-                    if (q == hipSuccess) {
-                        if (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != D.filter_seq)
-                            fatal("device filter result did not reach the host");
-                        break;
-                    }
-                    if (q != hipErrorNotReady) check(q, "search");
-                }
-                __builtin_ia32_pause();
-            }
-        } else {
-            if (!lean) check(hipEventRecord(D.ev[3], st), "event");
-            check(hipStreamSynchronize(st), "search");
-        }
+        if (!lean) check(hipEventRecord(D.ev[3], st), "event");
+        check(hipStreamSynchronize(st), "search");
         sync_wait += now_ms() - t_sync0;
         // a strip part gave up waiting for its group's first part: this
         // launch's scores are incomplete -- the caller runs the search again
@@ -2963,10 +2671,8 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             const uint32_t nc = D.h_fbuf[0];
             const uint2* cand = (const uint2*)(D.h_fbuf + kFilterHeader);
             std::vector<uint2> more;
-            // (the filter wrote its result to pinned memory itself: up to h_cand_cap)
-            const size_t have = host_direct ? D.h_cand_cap : D.cand_first;
             D.cand_hint = nc;
-            if (nc > have) {
+            if (nc > D.cand_first) {
                 more.resize(nc);
                 check(hipMemcpy(more.data(), D.d_fbuf + kFilterHeader, 8 * (size_t)nc, hipMemcpyDeviceToHost),
                       "D2H candidates");
@@ -3039,13 +2745,9 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             check(hipEventElapsedTime(&t, D.ev[0], D.ev[1]), "elapsed");
             kms += t;
         }
-        if (!lean || side_tier) {
-            check(hipEventElapsedTime(&t, ev_k1, side_tier ? D.ev[8] : D.ev[2]), "elapsed");
+        if (!lean) {
+            check(hipEventElapsedTime(&t, ev_k1, D.ev[2]), "elapsed");
             wms += t;
-        }
-        if (!spin && !lean) {
-            // (the spinning path has no copy: the filter's own time is in the
-            // kernel trace, d2h_ms stays 0)
             check(hipEventElapsedTime(&t, D.ev[2], D.ev[3]), "elapsed");
             dms += t;
         }

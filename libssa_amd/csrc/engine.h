@@ -31,29 +31,7 @@ struct DeviceDB {
     uint64_t generation = ~0ull;
     int symtype = -1, strands = -1, dgencode = -1;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[9] = {};                // [8]: the int32 tier's end when it runs beside the filter
-    hipEvent_t ev_fork = nullptr;         // a recorded search's fork to the long-entry streams
-    // graph-eligible searches' stream operations as instantiated HIP graphs
-    // (engine.cpp run_ops), a few launch plans at once (least recently used
-    // replaced): a search whose operations have the shape of a cached graph's
-    // replays it with its changed arguments set on the nodes
-    struct SearchGraph {
-        hipGraph_t g = nullptr;
-        hipGraphExec_t exec = nullptr;
-        std::vector<StreamOp> ops;
-        std::vector<hipGraphNode_t> nodes;   // per op: its node (kernels, copies, sets)
-        uint64_t used = 0;
-        void reset();
-    };
-    static constexpr size_t kGraphs = 8;
-    struct SearchGraphs {
-        SearchGraph slot[kGraphs];
-        bool broken = false;                 // a capture or instantiation failed: call by call from then on
-        uint64_t clock = 0;
-        void reset() {
-            for (auto& x : slot) x.reset();
-        }
-    } graph;
+    hipEvent_t ev[8] = {};
     EntryMeta meta;
     uint32_t ngroups = 0;
     uint64_t nblocks = 0;                 // 1 KiB residue blocks
@@ -152,7 +130,6 @@ struct DeviceDB {
     // grid (a hint only -- the tier loops over any list length)
     uint32_t tier_hint = 0;
     bool cnt_dirty = true;
-    uint32_t filter_seq = 0;              // the last FilterArgs::host_seq (never 0)
     uint32_t filter_epoch = 0;            // the last FilterArgs::epoch (one-pass filter)
     uint32_t* d_smax = nullptr;
     size_t smax_cap = 0;
@@ -244,7 +221,6 @@ struct SearchScores {
     uint32_t part_retries = 0;           // 1: a strip-part wait timed out, the search ran again without parts
     uint32_t rare_merged = 0;            // compact codes scored through one upper-bound class (0: none)
     uint32_t rare_rescored = 0;          // forwarded merged-code entries re-scored exactly
-    uint32_t graph = 0;                  // 0 direct, 1 captured into a new graph, 2 replayed (stats graph)
     int64_t get(size_t v, size_t e) const {
         const int32_t x = s32[v * entries + e];
         if (x != INT32_MIN) return x;

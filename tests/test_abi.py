@@ -219,6 +219,24 @@ def test_chunk_size_zero_message(tmp_path):
         in r.stdout
 
 
+def test_removed_options_warn_as_unknown(capfd):
+    """The options that lost their A/B and left the library are
+    unknown names now: ssa_amd_set_option warns at the default output mode
+    (OUTPUT_WARNING) and changes nothing; a name it knows stays quiet."""
+    libc = ctypes.CDLL(None)
+
+    def warned(name):
+        capfd.readouterr()
+        S.set_option(name, 1)
+        libc.fflush(None)
+        return f"unknown option {name}" in capfd.readouterr().out
+
+    S.set_output_mode(S.OUTPUT_WARNING)
+    for name in ("graph", "side_tier", "filter_host", "pair_split", "pair_prio_groups"):
+        assert warned(name), name
+    assert not warned("long_latency")       # (1 is its default)
+
+
 def test_replay_entry_point_is_host_only():
     """ssa_amd_replay is the reference heap over a log (no GPU needed)."""
     from oracle import pyoracle as po
