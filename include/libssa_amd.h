@@ -86,6 +86,24 @@ typedef struct {
     double slot_search_ms[16];   /* per slot: host time of its device search and shard replay */
 } ssa_amd_stats_t;
 
+typedef struct {
+    uint64_t pairs;        /* pairs of the last ssa_amd_score_pairs call */
+    uint64_t cells;        /* sum of qlen * dlen */
+    uint64_t swept_cells;  /* cells the waves walked: padding lanes, rows and columns included
+                              (cells of device pairs / swept_cells = the packing efficiency) */
+    uint64_t host_pairs;   /* pairs scored on the host: the exact int64 path and empty-side pairs */
+    uint32_t groups;       /* groups of 64 pairs, one per wave */
+    uint32_t chunks;       /* pack / upload / launch / copy rounds (option "pairs_chunk") */
+    uint32_t launches;     /* kernel launches */
+    uint32_t strip_rows;   /* query rows per strip of pairs_kernel */
+    double total_ms;       /* host wall time of the call */
+    double pack_ms;        /* host: ordering and lane-interleaved packing */
+    double kernel_ms;      /* HIP-event time of the kernel launches */
+    double host_ms;        /* host wall time of the exact host path */
+    int32_t device;        /* HIP device of the call, -1: none used */
+    char kernel[32];       /* "pairs_sw_i32" / "pairs_nw_i32" */
+} ssa_amd_pairs_stats_t;
+
 #define SSA_AMD_SW 0
 #define SSA_AMD_NW 1
 #define SSA_AMD_TOPK 0      /* sorted top-k, as sw_align/nw_align */
@@ -297,6 +315,35 @@ int ssa_amd_load_db( const char * path );
  * CIGAR (truncated to cap - 1 characters); returns the CIGAR length. */
 size_t ssa_amd_align_pair( int algo, const char * query, size_t qlen, const char * db, size_t dlen,
                            size_t region[4], char * cigar, size_t cap );
+
+/* Exact optimal scores of npairs independent pairs with the current matrix and
+ * gap penalties (init_score_matrix / init_constant_scores / init_gap_penalties).
+ * Sequences are mapped residue codes (< 32), as ssa_amd_align_pair takes them:
+ * pair i is q_codes[q_off[i] .. q_off[i+1]) against d_codes[d_off[i] .. d_off[i+1]).
+ * scores[i] is what sw_align / nw_align report for that pair (query = q side,
+ * DB sequence = d side: the search scores M[d][q]).  Returns 0, or non-zero
+ * (nothing written, nothing launched) for a NULL argument with npairs > 0,
+ * decreasing offsets, a code >= 32 or an unknown algo.
+ * An empty side is defined: SW scores 0; NW scores 0 when both sides are empty
+ * and gap_open + L * gap_extend against a side of length L.
+ * The batch is ordered by shape, packed 64 pairs to a wave and scored in int32
+ * by pairs_kernel on the current device (ssa_amd_set_device; one device, never
+ * the SSA_AMD_DEVICES slots); pairs int32 cannot score exactly -- a matrix
+ * entry outside int8, a positive gap penalty, a score bound near 2^29 -- and
+ * every pair when no HIP device is visible go through the int64 recurrences
+ * on the host, in parallel (set_thread_count).  An open DB, its device copy
+ * and ssa_amd_get_stats are left alone.  Options:
+ *   "pairs_chunk" N      pairs per pack / launch round (multiples of 64); 0 (default): as many as
+ *                        fit 256 MiB of device memory
+ *   "pairs_host" 0|1     1: every pair on the host path (default 0)
+ * Tracebacks: ssa_amd_align_pair on the pairs of interest. */
+int ssa_amd_score_pairs( int algo, const uint8_t * q_codes, const uint64_t * q_off,
+                         const uint8_t * d_codes, const uint64_t * d_off,
+                         size_t npairs, int64_t * scores );
+void ssa_amd_get_pairs_stats( ssa_amd_pairs_stats_t * out );
+/* ASCII -> DB-side residue codes of the current symbol type (us_map_sequence:
+ * unknown -> 0); writes min(len, cap) codes, returns len. */
+size_t ssa_amd_map_residues( const char * ascii, size_t len, char * out, size_t cap );
 
 /* The query buffers a search scores for the current symbol type and strands
  * (reference searcher.c:42-90): one q_seq_t per strand/frame view, codes as

@@ -75,6 +75,13 @@ class ssa_amd_stats_t(Structure):
                 ("slot_search_ms", c_double * 16)]
 
 
+class ssa_amd_pairs_stats_t(Structure):
+    _fields_ = [("pairs", c_uint64), ("cells", c_uint64), ("swept_cells", c_uint64), ("host_pairs", c_uint64),
+                ("groups", c_uint32), ("chunks", c_uint32), ("launches", c_uint32), ("strip_rows", c_uint32),
+                ("total_ms", c_double), ("pack_ms", c_double), ("kernel_ms", c_double), ("host_ms", c_double),
+                ("device", c_int32), ("kernel", ctypes.c_char * 32)]
+
+
 assert ctypes.sizeof(db_seq_t) == 32 and ctypes.sizeof(q_seq_t) == 24
 assert ctypes.sizeof(alignment_t) == 112 and ctypes.sizeof(alignment_list_t) == 16
 assert ctypes.sizeof(ssa_hit_t) == 24
@@ -91,7 +98,8 @@ EXPORTS = {
                       "ssa_amd_dist_unique_id", "ssa_amd_dist_unique_id_bytes", "ssa_amd_dist_init",
                       "ssa_amd_dist_finalize", "ssa_amd_gather_logs", "ssa_amd_merge_logs", "ssa_amd_get_timeline",
                       "ssa_amd_dist_available", "ssa_amd_dist_init_fake", "ssa_amd_dist_ranks", "ssa_amd_shard_bounds",
-                      "ssa_amd_get_devices"],
+                      "ssa_amd_get_devices", "ssa_amd_score_pairs", "ssa_amd_get_pairs_stats",
+                      "ssa_amd_map_residues"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -141,6 +149,9 @@ def load():
         "ssa_amd_get_timeline": ([c_void_p, c_size_t], c_size_t),
         "ssa_amd_dist_available": ([], c_int), "ssa_amd_dist_init_fake": ([c_int, c_int, c_int], c_int),
         "ssa_amd_dist_ranks": ([], c_int),
+        "ssa_amd_score_pairs": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+        "ssa_amd_get_pairs_stats": ([POINTER(ssa_amd_pairs_stats_t)], None),
+        "ssa_amd_map_residues": ([c_char_p, c_size_t, c_char_p, c_size_t], c_size_t),
         "ssa_amd_shard_bounds": ([c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_size_t)], c_int),
     }
     for name, (args, res) in sig.items():
@@ -352,6 +363,70 @@ def align_pair(algo, query_codes, db_codes):
     buf = ctypes.create_string_buffer(n + 1)
     L.ssa_amd_align_pair(algo, q, len(q), d, len(d), reg, buf, n + 1)
     return tuple(reg), buf.value.decode()
+
+
+def _concat_codes(seqs):
+    import numpy as np
+    off = np.zeros(len(seqs) + 1, np.uint64)
+    if seqs:
+        np.cumsum([len(s) for s in seqs], out=off[1:])
+    parts = [np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray)) else np.asarray(s, np.uint8)
+             for s in seqs]
+    codes = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    if codes.size == 0:
+        codes = np.zeros(1, np.uint8)
+    return np.ascontiguousarray(codes), off
+
+
+def score_pairs(algo, queries, targets):
+    """ssa_amd_score_pairs: the exact score of queries[i] against targets[i]
+    (two equal-length lists of uint8 residue-code arrays) as an int64 array --
+    what sw_align / nw_align report for query i against the one-entry DB
+    targets[i].  Raises ValueError when the library refuses the arguments."""
+    import numpy as np
+    if len(queries) != len(targets):
+        raise ValueError("score_pairs: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    return score_pairs_flat(algo, q, qo, d, do)
+
+
+def score_pairs_flat(algo, q_codes, q_off, d_codes, d_off):
+    """ssa_amd_score_pairs on the C layout itself: contiguous uint8 code
+    arrays and uint64 offset arrays of npairs + 1 entries each (no per-call
+    concatenation: what a caller with many pairs keeps around)."""
+    import numpy as np
+    for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
+        if a.dtype != t or not a.flags.c_contiguous:
+            raise ValueError("score_pairs_flat: contiguous uint8 codes and uint64 offsets expected")
+    if len(q_off) != len(d_off) or len(q_off) < 1:
+        raise ValueError("score_pairs_flat: offset arrays of npairs + 1 entries expected")
+    n = len(q_off) - 1
+    out = np.zeros(n, np.int64)
+    rc = load().ssa_amd_score_pairs(algo, q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data,
+                                    d_off.ctypes.data, n, out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ssa_amd_score_pairs refused its arguments ({rc})")
+    return out
+
+
+def pairs_stats():
+    """ssa_amd_get_pairs_stats: the last score_pairs call as a dict."""
+    s = ssa_amd_pairs_stats_t()
+    load().ssa_amd_get_pairs_stats(ctypes.byref(s))
+    d = {f: getattr(s, f) for f, _ in ssa_amd_pairs_stats_t._fields_}
+    d["kernel"] = d["kernel"].decode()
+    return d
+
+
+def map_residues(seq):
+    """ssa_amd_map_residues: ASCII -> DB-side residue codes (uint8 array) of
+    the current symbol type; unknown letters map to 0."""
+    import numpy as np
+    src = _b(seq)
+    out = ctypes.create_string_buffer(max(len(src), 1))
+    load().ssa_amd_map_residues(src, len(src), out, len(src))
+    return np.frombuffer(out.raw[:len(src)], np.uint8).copy()
 
 
 def search_batch(queries, algo, hitcount, bit_width=BIT_WIDTH_16):

@@ -617,6 +617,25 @@ size_t ssa_amd_align_pair(int algo, const char* query, size_t qlen, const char* 
     return c.size();
 }
 
+int ssa_amd_score_pairs(int algo, const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes,
+                        const uint64_t* d_off, size_t npairs, int64_t* scores) {
+    return score_pairs(algo, q_codes, q_off, d_codes, d_off, npairs, scores);
+}
+
+void ssa_amd_get_pairs_stats(ssa_amd_pairs_stats_t* out) {
+    if (out) *out = pairs_stats();
+}
+
+size_t ssa_amd_map_residues(const char* ascii, size_t len, char* out, size_t cap) {
+    const int st = cfg().symtype;
+    const signed char* map = (st == AMINOACID || st == TRANS_QUERY) ? map_aa() : map_nt();
+    for (size_t i = 0; ascii && out && i < len && i < cap; i++) {
+        const signed char m = map[(unsigned char)ascii[i]];
+        out[i] = m >= 0 ? (char)m : 0;
+    }
+    return len;
+}
+
 size_t ssa_amd_query_views(p_query query, q_seq_t* out, size_t cap) {
     if (!query) return 0;
     const std::vector<QueryView> v = query_views(query);
@@ -667,6 +686,8 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "plan_cache")) cfg().plan_cache = (int)value;
     else if (!strcmp(name, "long_latency")) cfg().long_latency = (int)value;
     else if (!strcmp(name, "filter_onepass")) cfg().filter_onepass = (int)value;
+    else if (!strcmp(name, "pairs_chunk")) cfg().pairs_chunk = (int)std::max(0L, std::min(value, 1L << 30));
+    else if (!strcmp(name, "pairs_host")) cfg().pairs_host = (int)value;
     else if (!strcmp(name, "filter_prefix_regs")) set_filter_prefix_regs((int)value);
     else print_warning("unknown option %s", name);
 }

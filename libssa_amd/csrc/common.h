@@ -81,6 +81,8 @@ struct Config {
     int lean_events = 1;                  // 1 (default): no timing markers around the upload, the tier and the filter
                                           // (stats upload_ms / wide_ms / d2h_ms stay 0; kernel_ms kept;
                                           // C2 +0.5 %, profiles/r05/ab/lean_events)
+    int pairs_chunk = 0;                  // ssa_amd_score_pairs: pairs per pack / launch round; 0: by a byte budget
+    int pairs_host = 0;                   // 1: every pair of ssa_amd_score_pairs on the exact host path
     int rare_merge = 0;                   // 1: when the query's residue classes leave the pair table too big for
                                           // three workgroups per CU, the rarest classes share one upper-bound
                                           // class and the forwarded entries holding them are re-scored exactly
@@ -177,5 +179,11 @@ void sort_hits(std::vector<Hit>& v);   // score desc, id desc (util.h:12)
 // align.cpp: region {q begin, q end, db begin, db end} and CIGAR of a pair
 std::string traceback(int algo, const uint8_t* q, size_t qn, const uint8_t* d, size_t dn, size_t region[4]);
 void compute_alignments(p_alignment_list L, int algo);
+
+// ------------------------------------------------------------ pair batches
+// pairs.cpp: ssa_amd_score_pairs and its statistics
+int score_pairs(int algo, const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off,
+                size_t npairs, int64_t* scores);
+const ssa_amd_pairs_stats_t& pairs_stats();
 
 }  // namespace ssa
