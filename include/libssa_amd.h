@@ -84,6 +84,10 @@ typedef struct {
     int32_t slot_device[16];     /* per slot: its HIP device */
     double slot_kernel_ms[16];   /* per slot: HIP-event time of its DP kernels */
     double slot_search_ms[16];   /* per slot: host time of its device search and shard replay */
+    uint32_t part_units;     /* pair kernel strip parts: work units of second and later parts in the last
+                                search's launch (0: the groups ran whole) */
+    uint32_t pruned_units;   /* of those, skipped because no entry of theirs could still reach the top-k
+                                (option "topk_prune"; scores and hits unaffected) */
 } ssa_amd_stats_t;
 
 typedef struct {
@@ -198,6 +202,10 @@ void ssa_amd_get_stats( ssa_amd_stats_t * out );
  *   "part_wait_us" N     bound of a strip part's wait for its group's first part (default
  *                        2000000); a timed-out wait makes the search run again without parts
  *                        (stats part_retries), results unchanged
+ *   "topk_prune" 1|0     1 (default): a single-query SW top-k search (sw_align, ssa_amd_search TOPK; width
+ *                        16 or 64, k <= 64, one device) whose groups run as strip parts skips the
+ *                        later parts of every work unit whose entries provably stay below the k-th
+ *                        best score (stats part_units / pruned_units); hits are identical; 0: never
  *   "rare_merge" 0|1     1 (default 0): when a query's residue classes leave the pair table too big
  *                        for three workgroups per CU, the rarest classes share one class scoring
  *                        the maximum of their rows, and the entries holding them that the device

@@ -263,8 +263,11 @@ void publish_stats(const std::vector<SearchScores>& sc, const std::vector<SlotPl
     snprintf(S.long_kernel, sizeof S.long_kernel, "%s", sc.empty() ? "" : sc[0].long_kernel);
     S.part_retries = 0;
     S.rare_merged = S.rare_rescored = 0;
+    S.part_units = S.pruned_units = 0;
     for (const SearchScores& x : sc) {
         S.part_retries += x.part_retries;
+        S.part_units += x.part_units;
+        S.pruned_units += x.pruned_units;
         S.rare_merged = std::max(S.rare_merged, x.rare_merged);
         S.rare_rescored += x.rare_rescored;
     }
@@ -280,8 +283,11 @@ void run_search(p_query q, int algo, size_t k, int bw, bool want_log, SearchResu
     std::vector<SearchScores> sc(plan.size());
     std::vector<std::vector<Hit>> logs(plan.size());
     std::vector<double> slot_ms(plan.size(), 0.0);
+    // top-k pruning: one device, a sorted list and no log --
+    // the insertion log would show the skipped entries' lower-bound scores
+    const bool prune = plan.size() == 1 && !want_log;
     if (plan.size() == 1) {
-        device_search(device_db(0), R.views, algo, k, bw, sc[0]);
+        device_search(device_db(0), R.views, algo, k, bw, sc[0], nullptr, prune);
         slot_ms[0] = now_ms() - t0;
     } else {
         // one persistent host thread per device slot (the caller's for slot
@@ -300,6 +306,16 @@ void run_search(p_query q, int algo, size_t k, int bw, bool want_log, SearchResu
     TopK heap(k);
     if (plan.size() == 1) {
         replay(sc[0], device_db(0).meta, R.views, heap, want_log ? &R.hits : nullptr);
+        if (sc[0].pruned_units > 0 && heap.tie_evicted()) {
+            // an entry tied at the k-th score left the heap: which of the
+            // tied ones stay depends on the heap's layout, and so on the exact
+            // scores of entries the pruned search only bounded from below
+            //  -- this search runs again with every score exact
+            device_search(device_db(0), R.views, algo, k, bw, sc[0], nullptr, false);
+            slot_ms[0] = now_ms() - t0;
+            heap = TopK(k);
+            replay(sc[0], device_db(0).meta, R.views, heap, nullptr);
+        }
     } else {
         for (const auto& L : logs)
             for (const Hit& h : L)
@@ -674,6 +690,7 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "part_wait_us")) cfg().part_wait_us = std::max(0L, value);
     else if (!strcmp(name, "rescore32")) cfg().rescore32 = (int)value;
     else if (!strcmp(name, "rare_merge")) cfg().rare_merge = (int)value;
+    else if (!strcmp(name, "topk_prune")) cfg().topk_prune = (int)value;
     else if (!strcmp(name, "sync_spin")) cfg().sync_spin = (int)value;
     else if (!strcmp(name, "lean_events")) cfg().lean_events = (int)value;
     else if (!strcmp(name, "long16_rows")) cfg().long16_rows = (int)value;
@@ -738,7 +755,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         std::iota(ord.begin(), ord.end(), (size_t)0);
         std::stable_sort(ord.begin(), ord.end(),
                          [&](size_t x, size_t y) { return qviews[x][0].len < qviews[y][0].len; });
-        uint32_t launches = 0, retries = 0;
+        uint32_t launches = 0, retries = 0, punits = 0, pruned = 0;
         uint64_t ncand = 0;
         for (size_t b0 = 0; b0 < nq; b0 += kMaxBatchPipe) {
             const size_t b1 = std::min(nq, b0 + kMaxBatchPipe);
@@ -752,6 +769,8 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
                 kms += stats().kernel_ms;
                 cells += stats().cells;
                 retries += stats().part_retries;
+                punits += stats().part_units;
+                pruned += stats().pruned_units;
                 ncand += stats().filter_candidates;
                 launches++;
                 const size_t n = std::min(hitcount, R.hits.size());
@@ -768,6 +787,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
             device_search(D, vs, al, hitcount, bit_width, agg, &sc);
             kms += agg.kernel_ms;
             retries += agg.part_retries;
+            punits += agg.part_units;
             launches += agg.fused_views ? 1u : (uint32_t)vs.size();
             for (size_t bi = b0; bi < b1; bi++) {
                 const size_t i = ord[bi];
@@ -791,6 +811,8 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         S.cells = cells;
         S.kernel_launches = launches;
         S.part_retries = retries;
+        S.part_units = punits;
+        S.pruned_units = pruned;
         S.filter_candidates = ncand;
         S.search_ms = now_ms() - t0;
         S.total_searches = before.total_searches + nq;
@@ -798,7 +820,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         S.total_search_ms = before.total_search_ms + S.search_ms;
         return total;
     }
-    uint32_t retries = 0, launches = 0;
+    uint32_t retries = 0, launches = 0, punits = 0, pruned = 0;
     uint64_t ncand = 0;
     for (size_t i = 0; i < nq; i++) {
         test_configuration(queries[i]);
@@ -807,6 +829,8 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         kms += stats().kernel_ms;
         cells += stats().cells;
         retries += stats().part_retries;
+        punits += stats().part_units;
+        pruned += stats().pruned_units;
         ncand += stats().filter_candidates;
         launches += stats().kernel_launches;
         const size_t n = std::min(hitcount, R.hits.size());
@@ -823,6 +847,8 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
     S.kernel_ms = kms;
     S.cells = cells;
     S.part_retries = retries;
+    S.part_units = punits;
+    S.pruned_units = pruned;
     S.filter_candidates = ncand;
     S.kernel_launches = launches;
     S.search_ms = now_ms() - t0;

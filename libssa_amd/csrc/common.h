@@ -83,6 +83,8 @@ struct Config {
                                           // C2 +0.5 %, profiles/r05/ab/lean_events)
     int pairs_chunk = 0;                  // ssa_amd_score_pairs: pairs per pack / launch round; 0: by a byte budget
     int pairs_host = 0;                   // 1: every pair of ssa_amd_score_pairs on the exact host path
+    int topk_prune = 1;                   // SW top-k searches on the pair kernel skip the strip parts of groups
+                                          // that can no longer reach the top-k (StripArgs::prune)
     int rare_merge = 0;                   // 1: when the query's residue classes leave the pair table too big for
                                           // three workgroups per CU, the rarest classes share one upper-bound
                                           // class and the forwarded entries holding them are re-scored exactly
@@ -168,10 +170,15 @@ public:
     size_t size() const { return a_.size(); }
     bool full() const { return a_.size() >= k_; }
     int64_t root_score() const { return a_.empty() ? INT64_MIN : a_[0].score; }
+    // an element scoring what the root scores now was evicted: which of the
+    // elements tied at the k-th score remain then depends on the heap's
+    // layout, i.e. on every lower score fed before
+    bool tie_evicted() const { return !a_.empty() && evicted_max_ == a_[0].score; }
     std::vector<Hit> sorted() const;
 private:
     size_t k_;
     std::vector<Hit> a_;
+    int64_t evicted_max_ = INT64_MIN;     // largest score ever evicted (they only grow)
 };
 void sort_hits(std::vector<Hit>& v);   // score desc, id desc (util.h:12)
 

@@ -1372,7 +1372,7 @@ bool batch_pipelinable(size_t nqueries, size_t k) {
 // of that launch are not used and the caller runs the search again without
 // parts.
 static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views, int algo, size_t k, int bw,
-                               SearchScores& out, std::vector<SearchScores>* indep, bool no_parts) {
+                               SearchScores& out, std::vector<SearchScores>* indep, bool no_parts, bool allow_prune) {
     check(hipSetDevice(D.device), "hipSetDevice");
     const Config& C = cfg();
     const size_t E = D.meta.size();
@@ -1394,6 +1394,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     out.cells = 0;
     out.cand.clear();
     out.dev_o8 = out.dev_o16 = 0;
+    out.part_units = out.pruned_units = 0;
     // the reference's overflow counters (counters.hip): per (view, entry)
     // flags, summed on the device after the last view -- only when someone
     // observes them (m_run prints them at OUTPUT_INFO, manager.c:157-160;
@@ -1627,6 +1628,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     char lkname[24] = "";                // long-entry kernel(s) of view 0 (stats)
     uint32_t lentries = 0;
     bool parts_used = false;                 // some view ran strip parts (their wait-timeout word is read back)
+    bool want_prune = false;                 // the pair launch skips parts that cannot reach the top-k
 
     for (size_t v = 0; v < V; v++) {
         const QueryView& qv = views[v];
@@ -2116,6 +2118,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
         // pair kernel until their workgroups have started -- they are the
         // critical path and must be placed before the pair kernel's fill the
         // CUs' LDS
+        uint32_t pl_parts = 1, pl_ps = 0, pl_quads = 0;   // the pair launch's strip parts (1: whole groups)
         if (use_pair) {
             TableArgs ta{};
             ta.query = D.d_query;
@@ -2139,6 +2142,69 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             {
                 const uint32_t T = main_strips + (tail_np > 0 ? 1u : 0u);
                 if (C.pair_ticket || (!no_parts && strip_parts(T) > 1)) ta.zero_ticket = gate + 1;
+                // top-k pruning (StripArgs::prune): the SW pair kernel with
+                // strip parts, one query view whose scores go through the
+                // device filter into one sorted list -- not where every exact
+                // score is observed (the overflow counters, the 8-bit
+                // cascade's included; the timeline) or a score is an upper
+                // bound (the rare-code merge)
+                want_prune = allow_prune && C.topk_prune && !nw && V == 1 && !ind && out.sparse && !want_counts &&
+                             bw != BIT_WIDTH_8 && !merge && !C.timeline && nmax16 > 0;
+            }
+            // strip parts: the launch's last work units become a fraction of a
+            // group (kernels.h StripArgs::nparts).  Planned here, ahead of the
+            // tables kernel, which writes the launch's pruning block
+            if (!fused || v + 1 == V) {
+                const uint32_t T = main_strips + (tail_np > 0 ? 1u : 0u);
+                const size_t nqf = fused ? V : 1;
+                uint32_t parts = no_parts ? 1u : strip_parts(T);
+                if (fused) parts = std::min(parts, 2u);   // (a fused batch's layout holds two row buffers)
+                if (parts > 2 && !D.d_rowbuf3 && D.ngroups > long_groups) {
+                    // the third part's row buffer (4 B per residue slot); without
+                    // the memory for it the search runs two parts
+                    if (piped && v > 0) check(hipStreamSynchronize(st), "sync");
+                    if (hipMalloc((void**)&D.d_rowbuf3, (size_t)D.nblocks * 4096) != hipSuccess) {
+                        (void)hipGetLastError();
+                        D.d_rowbuf3 = nullptr;
+                        parts = 2;
+                    }
+                }
+                if (parts > 1 && D.ngroups > long_groups) {
+                    pl_quads = (D.ngroups - long_groups + kPairWaves - 1) / kPairWaves;
+                    pl_ps = (T + parts - 1) / parts;
+                    pl_parts = (T + pl_ps - 1) / pl_ps;
+                    if (D.part_cap < pl_quads * nqf) {
+                        // the pruning block, then per quad (and query) its flag
+                        // and bound (kernels.h kPrune*)
+                        if (piped && v > 0) check(hipStreamSynchronize(st), "sync");
+                        const size_t bytes = ((size_t)kPruneWords + (size_t)pl_quads * nqf * 2) * 4;
+                        dfree(D.d_part);
+                        check(hipMalloc((void**)&D.d_part, bytes), "strip parts");
+                        check(hipMemsetAsync(D.d_part, 0, bytes, st), "memset");
+                        D.part_cap = pl_quads * nqf;
+                    }
+                    want_prune = want_prune && pl_parts > 1;
+                    ta.prune_blk = D.d_part;
+                    if (want_prune) {
+                        // rem: what the query rows below a part's last one can
+                        // add at most, on the codes the kernel scores with
+                        for (uint32_t p = 0; p + 1 < pl_parts && p < 2; p++) {
+                            int64_t rem = 0;
+                            for (size_t i = (size_t)(p + 1) * pl_ps * 2 * pnp; i < m; i++) {
+                                int64_t best = 0;
+                                for (uint32_t c = 0; c < A; c++)
+                                    best = std::max(best, vp.crow[(size_t)c * 32 + qv.seq[i]]);
+                                rem += best;
+                            }
+                            ta.prune_rem[p] = (uint32_t)std::min<int64_t>(rem, 1 << 30);
+                        }
+                        ta.prune_k = (uint32_t)k;
+                    }
+                } else {
+                    want_prune = false;
+                }
+            } else {
+                want_prune = false;
             }
             if (long_groups > 0 && C.long_gate && !long_only) {
                 // (at most what can be resident at once: every long workgroup
@@ -2194,40 +2260,16 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 }
                 b.timeline = nullptr;
             }
-            // strip parts: the launch's last work units become a fraction of a
-            // group (kernels.h StripArgs::nparts)
+            // strip parts, as planned ahead of the tables kernel
             if (!fused || v + 1 == V) {
-                const uint32_t T = main_strips + (tail_np > 0 ? 1u : 0u);
                 const size_t nqf = fused ? V : 1;
-                uint32_t parts = no_parts ? 1u : strip_parts(T);
-                if (fused) parts = std::min(parts, 2u);   // (a fused batch's layout holds two row buffers)
-                if (parts > 2 && !D.d_rowbuf3 && D.ngroups > long_groups) {
-                    // the third part's row buffer (4 B per residue slot); without
-                    // the memory for it the search runs two parts
-                    if (piped && v > 0) check(hipStreamSynchronize(st), "sync");
-                    if (hipMalloc((void**)&D.d_rowbuf3, (size_t)D.nblocks * 4096) != hipSuccess) {
-                        (void)hipGetLastError();
-                        D.d_rowbuf3 = nullptr;
-                        parts = 2;
-                    }
-                }
-                if (parts > 1 && D.ngroups > long_groups) {
-                    const uint32_t quads = (D.ngroups - long_groups + kPairWaves - 1) / kPairWaves;
-                    const uint32_t ps = (T + parts - 1) / parts;
-                    parts = (T + ps - 1) / ps;
-                    if (D.part_cap < quads * nqf || D.smax_cap < (size_t)D.ngroups * 64 * nqf) {
+                const uint32_t parts = pl_parts, ps = pl_ps, quads = pl_quads;
+                if (parts > 1) {
+                    if (D.smax_cap < (size_t)D.ngroups * 64 * nqf) {
                         if (piped && v > 0) check(hipStreamSynchronize(st), "sync");
-                        if (D.part_cap < quads * nqf) {
-                            dfree(D.d_part);
-                            check(hipMalloc((void**)&D.d_part, (size_t)quads * nqf * 4), "strip parts");
-                            check(hipMemsetAsync(D.d_part, 0, (size_t)quads * nqf * 4, st), "memset");
-                            D.part_cap = quads * nqf;
-                        }
-                        if (D.smax_cap < (size_t)D.ngroups * 64 * nqf) {
-                            dfree(D.d_smax);
-                            check(hipMalloc((void**)&D.d_smax, (size_t)D.ngroups * 64 * nqf * 4), "strip-part maxima");
-                            D.smax_cap = (size_t)D.ngroups * 64 * nqf;
-                        }
+                        dfree(D.d_smax);
+                        check(hipMalloc((void**)&D.d_smax, (size_t)D.ngroups * 64 * nqf * 4), "strip-part maxima");
+                        D.smax_cap = (size_t)D.ngroups * 64 * nqf;
                     }
                     // this launch's handoff flag value (no per-launch clearing:
                     // older launches left smaller or different values; never 0,
@@ -2241,7 +2283,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     b.nquads = quads;
                     b.split_q0 = 0;            // (every quad is split)
                     b.split_q1 = quads;
-                    b.part_done = D.d_part;
+                    b.part_done = D.d_part + kPruneWords;
                     b.part_smax = D.d_smax;
                     b.part_err = gate + 2;
                     // (ticks of the 100 MHz s_memrealtime clock)
@@ -2260,6 +2302,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                         if (parts > 2) b.rowbuf3 = D.d_rowbuf3;
                     }
                     parts_used = true;
+                    out.part_units += (uint32_t)((parts - 1) * quads * nqf);
                 }
             }
             const int lnp = main_strips ? pnp : tail_np;
@@ -2510,6 +2553,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             // write to host memory is a dead kernel input)
             f.host_out = nullptr;
             f.host_fence = 0;
+            if (want_prune && !multi) f.pruned = D.d_part + kPruneCount;
             const size_t xcap_al = (D.exact_cap + 1) & ~(size_t)1;     // (int64 scores 8-byte aligned)
             if (merge) {
                 f.emask = D.d_emask;
@@ -2672,6 +2716,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             const uint2* cand = (const uint2*)(D.h_fbuf + kFilterHeader);
             std::vector<uint2> more;
             D.cand_hint = nc;
+            if (want_prune) out.pruned_units = D.h_fbuf[4];
             if (nc > D.cand_first) {
                 more.resize(nc);
                 check(hipMemcpy(more.data(), D.d_fbuf + kFilterHeader, 8 * (size_t)nc, hipMemcpyDeviceToHost),
@@ -2791,14 +2836,14 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
 }
 
 void device_search(DeviceDB& D, const std::vector<QueryView>& views, int algo, size_t k, int bw, SearchScores& out,
-                   std::vector<SearchScores>* indep) {
-    if (device_search_once(D, views, algo, k, bw, out, indep, false)) {
+                   std::vector<SearchScores>* indep, bool allow_prune) {
+    if (device_search_once(D, views, algo, k, bw, out, indep, false, allow_prune)) {
         out.part_retries = 0;
         return;
     }
     // (every stream of the search has been synchronised; the counters and
     // the wait flag are zeroed again at the start of the search)
-    if (!device_search_once(D, views, algo, k, bw, out, indep, true))
+    if (!device_search_once(D, views, algo, k, bw, out, indep, true, false))
         fatal("pair kernel: strip-part wait timed out with strip parts off");
     out.part_retries = 1;
 }

@@ -116,7 +116,8 @@ struct DeviceDB {
     size_t hmm_cap = 0;                   // lanes
     unsigned long long* d_cnt = nullptr;  // [kMaxBatchPipe][2]
     unsigned long long* h_cnt = nullptr;  // pinned mirror (+ 16 B: the gate block's error word)
-    // pair_kernel strip parts (StripArgs::nparts): per quad parts done, per lane running maxima
+    // pair_kernel strip parts (StripArgs::nparts): the pruning block (kPruneWords), then per quad
+    // parts done and pruning bound; per lane running maxima
     uint32_t* d_part = nullptr;
     size_t part_cap = 0;
     uint32_t part_epoch = 0;              // the last pair launch's handoff flag value (StripArgs::part_epoch)
@@ -221,6 +222,10 @@ struct SearchScores {
     uint32_t part_retries = 0;           // 1: a strip-part wait timed out, the search ran again without parts
     uint32_t rare_merged = 0;            // compact codes scored through one upper-bound class (0: none)
     uint32_t rare_rescored = 0;          // forwarded merged-code entries re-scored exactly
+    // top-k pruning (StripArgs::prune): later-part work units of the pair
+    // launch and how many of them were skipped; entries of a skipped unit
+    // carry a lower bound of their score, below the final k-th score
+    uint32_t part_units = 0, pruned_units = 0;
     int64_t get(size_t v, size_t e) const {
         const int32_t x = s32[v * entries + e];
         if (x != INT32_MIN) return x;
@@ -234,8 +239,11 @@ struct SearchScores {
 // own device filter pass, and (*indep)[v] receives query v's scores; `out`
 // then only carries the batch's aggregate timing.  Callers check
 // batch_pipelinable() first.
+// allow_prune: the caller replays `out` alone into one sorted top-k list, so
+// the pair kernel may skip strip parts that cannot reach it (option
+// "topk_prune"; api.cpp run_search)
 void device_search(DeviceDB& D, const std::vector<QueryView>& views, int algo, size_t k, int bw, SearchScores& out,
-                   std::vector<SearchScores>* indep = nullptr);
+                   std::vector<SearchScores>* indep = nullptr, bool allow_prune = false);
 bool batch_pipelinable(size_t nqueries, size_t k);
 constexpr size_t kMaxBatchPipe = 16;    // queries per pipelined sub-batch (one fused launch when their plans agree)
 static_assert(kMaxBatchPipe == (size_t)kMaxFuse, "a sub-batch fuses into one pair_kernel launch");

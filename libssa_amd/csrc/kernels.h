@@ -106,7 +106,8 @@ struct StripArgs {
     // units 0 .. nquads-1 like part 0): units nquads .. are the later parts
     // of the split quads, part by part
     uint32_t split_q0, split_q1;
-    uint32_t* part_done;       // [nquads] part_epoch + q once the quad's part q is done (never cleared)
+    uint32_t* part_done;       // [nquads][2] part_epoch + q once the quad's part q is done (never cleared),
+                               // and the quad's pruning bound; the pruning block lies before it (below)
     uint32_t part_epoch;       // this launch's flag base: a multiple of 4, above every earlier launch's values
     uint32_t* part_smax;       // [ngroups * 64]
     uint32_t* part_err;        // set when a wait timed out (the host then runs the search again without parts)
@@ -131,6 +132,29 @@ struct StripArgs {
     // code count
     const uint4* paddr;
 };
+// pair_kernel, SW top-k searches: later parts that cannot reach the top-k are
+// skipped (DESIGN.md §3.1 "top-k pruning").  Nothing of it is a kernel
+// argument: used after the strips, an argument stays in a scalar register
+// across them, and the strips have none to spare (a first version with seven
+// more of them ran every search 1 % slower, pruned or not).  part_done points
+// kPruneWords dwords into its allocation, the block before it holds the
+// search's pruning state, written by the tables kernel
+// (TableArgs::prune_blk), and the quads' entries are pairs (flag, bound).
+//   k (0: pruning off), rem[2]: the list length and, per part boundary, the
+//     sum of the remaining query rows' largest non-negative profile values;
+//   lock, tau, list: part 0 offers its lanes' exact maxima over its rows to
+//     the list of the k largest; tau = its smallest once full, a lower bound
+//     of the final k-th score;
+//   count: the units skipped.
+// Every part but the last publishes as its quad's bound the most any of the
+// quad's entries can still score below its last row i_b: max over lanes of
+// max_j H(i_b, j), plus rem.  A later part whose bound is below tau writes its
+// lanes' maxima so far as their scores and returns.
+constexpr uint32_t kPruneLock = 0, kPruneTau = 1, kPruneCount = 2, kPruneK = 3, kPruneRem = 4, kPruneList = 16,
+                   kPruneWords = kPruneList + 64;
+// bound values above every score: never skip (a lane the part-0 maximum leaves
+// undecided) / an earlier part of the quad was skipped
+constexpr uint32_t kBoundNever = 0xffffffffu, kBoundSkipped = 0xfffffffeu;
 
 // Long DB entries (long_kernel): the query rows split over the lanes of W
 // waves (RL consecutive rows per lane, passes of W*64*RL rows), DB columns
@@ -273,6 +297,9 @@ struct FilterArgs {
     // null: the three launches.
     uint32_t* pass;
     uint32_t epoch;
+    // single view: the pair kernel's skipped-unit count (kPruneCount),
+    // copied into counters[4] like status; null: none
+    const uint32_t* pruned;
 };
 constexpr int kFilterSeqWord = 15;    // header word that carries FilterArgs::host_seq
 hipError_t launch_filter(const FilterArgs& a, hipStream_t st);
@@ -427,6 +454,10 @@ struct TableArgs {
     uint32_t* zero_ticket;     // StripArgs::ticket, cleared by thread 0 (may be null)
     uint32_t* zero_hdr;        // nzero_hdr dwords cleared by block 0 (the filter pass's counters,
     uint32_t nzero_hdr;        // when the re-score tier runs beside the filter instead of before it)
+    // the pair launch's pruning block (kPrune*, before StripArgs::part_done),
+    // written by block 0: k, rem, everything else 0; null: none
+    uint32_t* prune_blk;
+    uint32_t prune_k, prune_rem[2];
 };
 hipError_t launch_pair_tables(const TableArgs& a, hipStream_t st);
 // dst (device) <- src (pinned host), bytes a multiple of 4: a kernel on st

@@ -763,6 +763,7 @@ __global__ void __launch_bounds__(256) filter_select(const FilterArgs a0) {
     const uint32_t tid = blockIdx.x * 256 + threadIdx.x;
     if (tid < a.nviews) a.counters[3 + tid] = a.ovf_count[(size_t)tid * a.ovf_stride];
     if (tid == 0 && a.status) a.counters[2] = *a.status;
+    if (tid == 0 && a.pruned) a.counters[4] = *a.pruned;
     const uint32_t e0 = tid * kSelectPer;
     if (e0 < a.n) {
         int32_t x[kSelectPer];
@@ -968,6 +969,7 @@ __global__ void __launch_bounds__(256) filter_onepass(const FilterArgs a0) {
     if (b == 0) {
         for (uint32_t v = threadIdx.x; v < a.nviews; v += 256) a.counters[3 + v] = a.ovf_count[(size_t)v * a.ovf_stride];
         if (threadIdx.x == 0 && a.status) a.counters[2] = *a.status;
+        if (threadIdx.x == 0 && a.pruned) a.counters[4] = *a.pruned;
     }
 #pragma unroll
     for (int i = 0; i < MW; i++) {
@@ -1039,6 +1041,10 @@ __global__ void __launch_bounds__(256) pair_tables_kernel(const TableArgs a) {
     if (a.zero && blockIdx.x == 0 && threadIdx.x == 0) *a.zero = 0;
     if (a.zero_ticket && blockIdx.x == 0 && threadIdx.x == 0) *a.zero_ticket = 0;
     if (a.zero_hdr && blockIdx.x == 0 && threadIdx.x < a.nzero_hdr) a.zero_hdr[threadIdx.x] = 0;
+    if (a.prune_blk && blockIdx.x == 0 && threadIdx.x < kPruneWords) {
+        const uint32_t t = threadIdx.x;
+        a.prune_blk[t] = t == kPruneK ? a.prune_k : t == kPruneRem ? a.prune_rem[0] : t == kPruneRem + 1 ? a.prune_rem[1] : 0u;
+    }
     if (a.gate && blockIdx.x == 0 && threadIdx.x == 0) {
         // the long entries' workgroups (another stream) start first; bounded
         // at ~20 ms of the 100 MHz real-time counter, so a gate that is never
@@ -1105,6 +1111,11 @@ hipError_t launch_pair_tables(const TableArgs& a, hipStream_t st) {
         }
         if (a.zero_ticket) {
             const hipError_t e = op_set(a.zero_ticket, 0, 4, st);
+            if (e != hipSuccess) return e;
+        }
+        if (a.prune_blk) {
+            // (no table, no pair launch: pruning off)
+            const hipError_t e = op_set(a.prune_blk, 0, 4 * kPruneWords, st);
             if (e != hipSuccess) return e;
         }
         return a.zero ? op_set(a.zero, 0, 4, st) : hipSuccess;

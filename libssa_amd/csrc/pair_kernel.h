@@ -123,6 +123,85 @@ __device__ __forceinline__ uint4 load_quad(__amdgpu_buffer_rsrc_t rs, uint32_t v
     return make_uint4(x.x, x.y, x.z, x.w);
 }
 
+// ---- SW top-k pruning (kernels.h kPrune*) ------------------
+// (all lanes of the wave call these: the shuffles and ballots are wave-wide)
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+// score of an SW lane from its packed running maxima S of x = max(H - |R|, 0);
+// 0: H_max in [0, |R|] is undecided (the lane is re-scored exactly)
+__device__ __forceinline__ uint32_t sw_score(uint32_t S, uint32_t Rabs) {
+    const uint32_t slo = S & 0xffffu, shi = S >> 16;
+    const uint32_t smax = slo > shi ? slo : shi;
+    return smax == 0 && Rabs != 0 ? 0u : smax + Rabs;
+}
+// A lane's result: its score, or its place in the exact re-score list.
+__device__ __forceinline__ void sw_emit(int32_t* scores, uint32_t* ovf_list, uint32_t* ovf_count, uint32_t ovf_cap,
+                                        uint32_t o, uint32_t gl, bool ovf, int32_t score) {
+    if (ovf) {
+        const uint32_t idx = atomicAdd(ovf_count, 1u);
+        if (idx < ovf_cap) ovf_list[idx] = gl;
+        scores[o] = INT32_MIN;
+    } else {
+        scores[o] = score;
+    }
+}
+// The wave offers its lanes' part-0 scores sc (0: none) to the list of the k
+// largest.  Only a wave with a lane above tau takes the lock (lane 0, a
+// bounded number of tries: a wave that does not get it skips its offer, which
+// leaves tau lower and still valid).  Under the lock the list lives one slot
+// per lane; the wave's candidates replace its smallest slots, largest first.
+// Every access is an agent-scope atomic (the XCDs' L2s are not coherent), and
+// the list's stores have completed before tau's, tau's before the unlock.
+__device__ __forceinline__ void prune_offer(uint32_t* pr, uint32_t k, uint32_t sc, int lane) {
+    bool cand = false;
+    uint32_t got = 0;
+    for (int t = 0; t < 16; t++) {
+        const uint32_t tau = __hip_atomic_load(pr + kPruneTau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cand = sc > tau;
+        if (__ballot(cand) == 0) return;
+        if (lane == 0) {
+            uint32_t exp = 0;
+            got = __hip_atomic_compare_exchange_strong(pr + kPruneLock, &exp, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_AGENT) ? 1u : 0u;
+        }
+        got = __builtin_amdgcn_readfirstlane(got);
+        if (got) break;
+        __builtin_amdgcn_s_sleep(8);
+    }
+    if (!got) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    uint32_t mine = (uint32_t)lane < k
+                        ? __hip_atomic_load(pr + kPruneList + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                        : 0xffffffffu;
+    bool dirty = false;
+    for (uint32_t it = 0; it < k; it++) {
+        const uint32_t c = wave_max_u32(cand ? sc : 0u);
+        const uint32_t mn = wave_min_u32(mine);
+        if (c <= mn) break;
+        const int slot = __ffsll((long long)__ballot(mine == mn)) - 1;
+        if (lane == slot) {
+            mine = c;
+            dirty = true;
+        }
+        const int src = __ffsll((long long)__ballot(cand && sc == c)) - 1;
+        if (lane == src) cand = false;
+    }
+    if (dirty) __hip_atomic_store(pr + kPruneList + lane, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t ntau = wave_min_u32(mine);      // 0 while a slot is empty
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane == 0) __hip_atomic_store(pr + kPruneTau, ntau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane == 0) __hip_atomic_store(pr + kPruneLock, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 template <int NP, bool NW, int NPT>
 __global__ void __launch_bounds__(64 * pair_waves(NP, NW), pair_occupancy(NP, NW))
 pair_kernel(const StripArgs a) {
@@ -169,16 +248,63 @@ pair_kernel(const StripArgs a) {
             // the search again without parts -- never a hang
             if (threadIdx.x == 0) {
                 const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-                while (__hip_atomic_load(a.part_done + (size_t)wg * nqs + qi, __ATOMIC_RELAXED,
+                bool done = true;
+                while (__hip_atomic_load(a.part_done + 2 * ((size_t)wg * nqs + qi), __ATOMIC_RELAXED,
                                          __HIP_MEMORY_SCOPE_AGENT) != a.part_epoch + part - 1) {
                     if (__builtin_amdgcn_s_memrealtime() - t0 >= a.part_wait) {
                         __hip_atomic_store(a.part_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        done = false;
                         break;
                     }
                     __builtin_amdgcn_s_sleep(4);
                 }
+                if (!NW) {
+                    // top-k pruning (kernels.h kPrune*; on when k != 0, one
+                    // query): nothing below the previous part's last row can
+                    // lift an entry of this quad to tau (or an earlier part
+                    // found so)
+                    uint32_t* const pr = a.part_done - kPruneWords;
+                    uint32_t skip = 0;
+                    if (done && pr[kPruneK] != 0) {
+                        const uint32_t bd = __hip_atomic_load(a.part_done + 2 * (size_t)wg + 1, __ATOMIC_RELAXED,
+                                                              __HIP_MEMORY_SCOPE_AGENT);
+                        const uint32_t tau = __hip_atomic_load(pr + kPruneTau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        skip = bd == kBoundSkipped || bd < tau ? 1u : 0u;
+                    }
+                    lds[1] = skip;
+                }
             }
             __syncthreads();
+            if (!NW && __builtin_amdgcn_readfirstlane(lds[1])) {
+                // the lanes' scores are their maxima so far, decoded as at the
+                // kernel's end; a later part of the quad is told to skip too
+                if (threadIdx.x == 0) {
+                    atomicAdd(a.part_done - kPruneWords + kPruneCount, 1u);
+                    if (part + 1 < a.nparts) {
+                        __hip_atomic_store(a.part_done + 2 * (size_t)wg + 1, kBoundSkipped, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                        __builtin_amdgcn_s_waitcnt(0);
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                        __hip_atomic_store(a.part_done + 2 * (size_t)wg, a.part_epoch + part, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                const uint32_t g = a.g_first + wg * W + wave;
+                if (part + 1 < a.nparts || g >= a.ngroups) return;
+                const uint32_t gl = g * 64 + lane;
+                const uint32_t o = a.lane_out[gl];
+                if (o == 0xffffffffu) return;
+                const uint32_t len = a.lane_len[gl];
+                if (len == 0) {
+                    a.scores[o] = 0;
+                    return;
+                }
+                const uint32_t sc = sw_score(__hip_atomic_load(a.part_smax + gl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                                             (uint32_t)(-a.gap_extend));
+                sw_emit(a.scores, a.ovf_list, a.ovf_count, a.ovf_cap, o, gl, len > a.nmax16 || (sc == 0 && a.gap_extend != 0),
+                        (int32_t)sc);
+                return;
+            }
         }
     }
     const uint32_t g = a.g_first + wg * W + wave;
@@ -548,12 +674,66 @@ pair_kernel(const StripArgs a) {
         // hand the group on: running maxima, then (after every wave's row
         // buffer stores and maxima are visible at agent scope) the part count
         if (!NW && active) __hip_atomic_store(smax + gl, S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // top-k pruning: the wave's bound of what its entries can still score
+        // below this part's last row i_b, and (part 0) its offer to tau
+        uint32_t* const pr = a.part_done - kPruneWords;
+        const uint32_t pk = NW ? 0u : __builtin_amdgcn_readfirstlane(pr[kPruneK]);
+        const bool prune0 = pk != 0;
+        uint32_t wbound = 0;
+        if (prune0 && active) {
+            // a lane that counts: a real entry the 16-bit patterns score exactly
+            const bool real = a.lane_out[gl] != 0xffffffffu && len != 0 && len <= a.nmax16;
+            const uint32_t sc = real ? sw_score(S, Rabs) : 0u;
+            // Hb = max_j H(i_b, j) over the lane's own columns, from the
+            // handoff boundary row this wave just wrote (low halves; column
+            // c's pattern is H + floor - |R| with the floor of column c + 1,
+            // as in the flush): one pass of device-scope quad loads
+            __builtin_amdgcn_s_waitcnt(0);
+            // (eight loads in flight; past the last quad: it again)
+            const uint32_t fl0b = (uint32_t)kF16Floor + s1 * 2 * NP * Rabs;   // row i_b, column 0
+            uint32_t x = 0;
+            for (uint32_t q0 = 0; q0 < nquads; q0 += 8) {
+                uint4 v[8];
+#pragma unroll
+                for (uint32_t i = 0; i < 8; i++) v[i] = load_quad<16>(rbr, lane16, min(q0 + i, nquads - 1) * 1024u);
+#pragma unroll
+                for (uint32_t i = 0; i < 8; i++) {
+                    const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+#pragma unroll
+                    for (uint32_t u = 0; u < 4; u++) {
+                        const uint32_t c = min(q0 + i, nquads - 1) * 4 + u;
+                        const uint32_t xc = psubsat16(w[u] & 0xffffu, (fl0b + c * Rabs) & 0xffffu);
+                        x = c < len ? max(x, xc) : x;
+                    }
+                }
+            }
+            // (a real lane left undecided by its part-0 maximum would be
+            // re-scored after every part: its quad is never skipped)
+            const uint32_t lb = !real ? 0u : sc == 0 ? kBoundNever : x + Rabs + pr[kPruneRem + (part == 0 ? 0 : 1)];
+            wbound = wave_max_u32(lb);
+            // (once per lane: tau is the k-th of k distinct entries)
+            if (part == 0) prune_offer(pr, pk, sc, lane);
+        }
         // every wave's device-scope stores complete, then one flag store
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __syncthreads();
+        if (prune0) {
+            // (the pair table is no longer read: its first dwords carry the waves' bounds)
+            // (the wave index anew: kept from the kernel's start it would be one more
+            // scalar register live across the DP loop)
+            if (lane == 0) lds[2 + (threadIdx.x >> 6)] = wbound;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                uint32_t bd = 0;
+                for (int w = 0; w < W; w++) bd = max(bd, lds[2 + w]);
+                __hip_atomic_store(a.part_done + 2 * (size_t)wg + 1, bd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __builtin_amdgcn_s_waitcnt(0);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            }
+        }
         if (threadIdx.x == 0)
-            __hip_atomic_store(a.part_done + (size_t)wg * nqs + qi, a.part_epoch + part, __ATOMIC_RELAXED,
+            __hip_atomic_store(a.part_done + 2 * ((size_t)wg * nqs + qi), a.part_epoch + part, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
@@ -569,22 +749,14 @@ pair_kernel(const StripArgs a) {
     int32_t score;
     bool ovf = len > a.nmax16;
     if (!NW) {
-        const uint32_t slo = S & 0xffffu, shi = S >> 16;
-        const uint32_t smax = slo > shi ? slo : shi;
         // 0 leaves H_max in [0, |R|] undecided: re-score exactly
-        ovf = ovf || (smax == 0 && Rabs != 0);
-        score = (int32_t)smax + (int32_t)Rabs;
+        score = (int32_t)sw_score(S, Rabs);
+        ovf = ovf || (score == 0 && Rabs != 0);
     } else {
         // back from the diagonal-relative value: + (i + j) R at (m-1, len-1)
         score = (int32_t)(cap_half ? cap >> 16 : cap & 0xffffu) - BASE + ((int32_t)m + (int32_t)len - 2) * R;
     }
-    if (ovf) {
-        const uint32_t idx = atomicAdd(ovf_count, 1u);
-        if (idx < a.ovf_cap) ovf_list[idx] = gl;
-        scores[o] = INT32_MIN;
-    } else {
-        scores[o] = score;
-    }
+    sw_emit(scores, ovf_list, ovf_count, a.ovf_cap, o, gl, ovf, score);
 }
 
 template <int NP, bool NW, int NPT>

@@ -209,6 +209,7 @@ bool TopK::add(const Hit& h) {
         return true;
     }
     if (!(a_[0].score < h.score)) return false;
+    evicted_max_ = a_[0].score;
     size_t p = 0, c = 1, n = a_.size();
     while (c < n) {
         if (c + 1 < n && a_[c + 1].score < a_[c].score) c++;
