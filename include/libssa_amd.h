@@ -88,6 +88,11 @@ typedef struct {
                                 search's launch (0: the groups ran whole) */
     uint32_t pruned_units;   /* of those, skipped because no entry of theirs could still reach the top-k
                                 (option "topk_prune"; scores and hits unaffected) */
+    uint32_t inplace_units;  /* work units of a pruned search that ran their remaining parts themselves, in the
+                                same workgroup, instead of leaving them to later units (option
+                                "prune_inplace_pct"); the later units of their groups return at once and
+                                are not counted as pruned */
+    uint32_t pruned_first;   /* of pruned_units, those skipped at the first part boundary */
 } ssa_amd_stats_t;
 
 typedef struct {
@@ -206,6 +211,10 @@ void ssa_amd_get_stats( ssa_amd_stats_t * out );
  *                        16 or 64, k <= 64, one device) whose groups run as strip parts skips the
  *                        later parts of every work unit whose entries provably stay below the k-th
  *                        best score (stats part_units / pruned_units); hits are identical; 0: never
+ *   "prune_inplace_pct" N  a pruned search's work unit that cannot be skipped at a part boundary runs
+ *                        its remaining parts itself, at once, when its best entry so far has reached
+ *                        N % (default 25) of the most the query rows so far can score; 0: never.
+ *                        Changes the schedule only, never a score (stats inplace_units)
  *   "rare_merge" 0|1     1 (default 0): when a query's residue classes leave the pair table too big
  *                        for three workgroups per CU, the rarest classes share one class scoring
  *                        the maximum of their rows, and the entries holding them that the device

@@ -263,11 +263,13 @@ void publish_stats(const std::vector<SearchScores>& sc, const std::vector<SlotPl
     snprintf(S.long_kernel, sizeof S.long_kernel, "%s", sc.empty() ? "" : sc[0].long_kernel);
     S.part_retries = 0;
     S.rare_merged = S.rare_rescored = 0;
-    S.part_units = S.pruned_units = 0;
+    S.part_units = S.pruned_units = S.inplace_units = S.pruned_first = 0;
     for (const SearchScores& x : sc) {
         S.part_retries += x.part_retries;
         S.part_units += x.part_units;
         S.pruned_units += x.pruned_units;
+        S.inplace_units += x.inplace_units;
+        S.pruned_first += x.pruned_first;
         S.rare_merged = std::max(S.rare_merged, x.rare_merged);
         S.rare_rescored += x.rare_rescored;
     }
@@ -691,6 +693,7 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "rescore32")) cfg().rescore32 = (int)value;
     else if (!strcmp(name, "rare_merge")) cfg().rare_merge = (int)value;
     else if (!strcmp(name, "topk_prune")) cfg().topk_prune = (int)value;
+    else if (!strcmp(name, "prune_inplace_pct")) cfg().prune_inplace_pct = (int)std::min(100L, std::max(0L, value));
     else if (!strcmp(name, "sync_spin")) cfg().sync_spin = (int)value;
     else if (!strcmp(name, "lean_events")) cfg().lean_events = (int)value;
     else if (!strcmp(name, "long16_rows")) cfg().long16_rows = (int)value;
@@ -755,7 +758,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         std::iota(ord.begin(), ord.end(), (size_t)0);
         std::stable_sort(ord.begin(), ord.end(),
                          [&](size_t x, size_t y) { return qviews[x][0].len < qviews[y][0].len; });
-        uint32_t launches = 0, retries = 0, punits = 0, pruned = 0;
+        uint32_t launches = 0, retries = 0, punits = 0, pruned = 0, inplace = 0, pfirst = 0;
         uint64_t ncand = 0;
         for (size_t b0 = 0; b0 < nq; b0 += kMaxBatchPipe) {
             const size_t b1 = std::min(nq, b0 + kMaxBatchPipe);
@@ -771,6 +774,8 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
                 retries += stats().part_retries;
                 punits += stats().part_units;
                 pruned += stats().pruned_units;
+                inplace += stats().inplace_units;
+                pfirst += stats().pruned_first;
                 ncand += stats().filter_candidates;
                 launches++;
                 const size_t n = std::min(hitcount, R.hits.size());
@@ -813,6 +818,8 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         S.part_retries = retries;
         S.part_units = punits;
         S.pruned_units = pruned;
+        S.inplace_units = inplace;
+        S.pruned_first = pfirst;
         S.filter_candidates = ncand;
         S.search_ms = now_ms() - t0;
         S.total_searches = before.total_searches + nq;
@@ -820,7 +827,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         S.total_search_ms = before.total_search_ms + S.search_ms;
         return total;
     }
-    uint32_t retries = 0, launches = 0, punits = 0, pruned = 0;
+    uint32_t retries = 0, launches = 0, punits = 0, pruned = 0, inplace = 0, pfirst = 0;
     uint64_t ncand = 0;
     for (size_t i = 0; i < nq; i++) {
         test_configuration(queries[i]);
@@ -831,6 +838,8 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         retries += stats().part_retries;
         punits += stats().part_units;
         pruned += stats().pruned_units;
+        inplace += stats().inplace_units;
+        pfirst += stats().pruned_first;
         ncand += stats().filter_candidates;
         launches += stats().kernel_launches;
         const size_t n = std::min(hitcount, R.hits.size());
@@ -849,6 +858,8 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
     S.part_retries = retries;
     S.part_units = punits;
     S.pruned_units = pruned;
+    S.inplace_units = inplace;
+    S.pruned_first = pfirst;
     S.filter_candidates = ncand;
     S.kernel_launches = launches;
     S.search_ms = now_ms() - t0;

@@ -85,6 +85,10 @@ struct Config {
     int pairs_host = 0;                   // 1: every pair of ssa_amd_score_pairs on the exact host path
     int topk_prune = 1;                   // SW top-k searches on the pair kernel skip the strip parts of groups
                                           // that can no longer reach the top-k (StripArgs::prune)
+    int prune_inplace_pct = 25;           // a pruned search's work unit that cannot be skipped at a part boundary
+                                          // runs its remaining parts itself, in the same workgroup, when its best
+                                          // lane has reached this share (%) of what the rows so far can give at
+                                          // most; 0: never (every later part as a work unit of its own)
     int rare_merge = 0;                   // 1: when the query's residue classes leave the pair table too big for
                                           // three workgroups per CU, the rarest classes share one upper-bound
                                           // class and the forwarded entries holding them are re-scored exactly

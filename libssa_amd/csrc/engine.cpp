@@ -1394,7 +1394,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     out.cells = 0;
     out.cand.clear();
     out.dev_o8 = out.dev_o16 = 0;
-    out.part_units = out.pruned_units = 0;
+    out.part_units = out.pruned_units = out.inplace_units = out.pruned_first = 0;
     // the reference's overflow counters (counters.hip): per (view, entry)
     // flags, summed on the device after the last view -- only when someone
     // observes them (m_run prints them at OUTPUT_INFO, manager.c:157-160;
@@ -2159,6 +2159,12 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 const size_t nqf = fused ? V : 1;
                 uint32_t parts = no_parts ? 1u : strip_parts(T);
                 if (fused) parts = std::min(parts, 2u);   // (a fused batch's layout holds two row buffers)
+                // a pruned search in auto mode cuts twice: early, after two
+                // strips, where the final scores' threshold already skips a
+                // unit without a strong hit, and where the two-part plan cuts,
+                // for the hits only the part-0 threshold can skip
+                bool early = want_prune && !no_parts && !fused && C.pair_parts == 0 && T >= 6;
+                if (early) parts = 3;
                 if (parts > 2 && !D.d_rowbuf3 && D.ngroups > long_groups) {
                     // the third part's row buffer (4 B per residue slot); without
                     // the memory for it the search runs two parts
@@ -2167,12 +2173,15 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                         (void)hipGetLastError();
                         D.d_rowbuf3 = nullptr;
                         parts = 2;
+                        early = false;
                     }
                 }
                 if (parts > 1 && D.ngroups > long_groups) {
                     pl_quads = (D.ngroups - long_groups + kPairWaves - 1) / kPairWaves;
                     pl_ps = (T + parts - 1) / parts;
-                    pl_parts = (T + pl_ps - 1) / pl_ps;
+                    pl_parts = early ? 3u : (T + pl_ps - 1) / pl_ps;
+                    // the strip index of each part boundary
+                    const uint32_t cuts[2] = {early ? 2u : pl_ps, early ? (T + 1) / 2 : 2 * pl_ps};
                     if (D.part_cap < pl_quads * nqf) {
                         // the pruning block, then per quad (and query) its flag
                         // and bound (kernels.h kPrune*)
@@ -2188,15 +2197,23 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     if (want_prune) {
                         // rem: what the query rows below a part's last one can
                         // add at most, on the codes the kernel scores with
+                        // prom: the share (option "prune_inplace_pct") of what
+                        // the rows above it can give at most, from which a unit
+                        // counts as promising and finishes in place
                         for (uint32_t p = 0; p + 1 < pl_parts && p < 2; p++) {
-                            int64_t rem = 0;
-                            for (size_t i = (size_t)(p + 1) * pl_ps * 2 * pnp; i < m; i++) {
+                            int64_t rem = 0, top = 0;
+                            const size_t row_b = (size_t)cuts[p] * 2 * pnp;
+                            for (size_t i = 0; i < m; i++) {
                                 int64_t best = 0;
                                 for (uint32_t c = 0; c < A; c++)
                                     best = std::max(best, vp.crow[(size_t)c * 32 + qv.seq[i]]);
-                                rem += best;
+                                (i < row_b ? top : rem) += best;
                             }
                             ta.prune_rem[p] = (uint32_t)std::min<int64_t>(rem, 1 << 30);
+                            const int64_t pct = std::min(std::max(C.prune_inplace_pct, 0), 100);
+                            ta.prune_prom[p] = pct == 0 ? 0xffffffffu
+                                                        : (uint32_t)std::min<int64_t>((top * pct + 99) / 100, 1 << 30);
+                            if (early) ta.prune_cut[p] = cuts[p];
                         }
                         ta.prune_k = (uint32_t)k;
                     }
@@ -2716,7 +2733,11 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             const uint2* cand = (const uint2*)(D.h_fbuf + kFilterHeader);
             std::vector<uint2> more;
             D.cand_hint = nc;
-            if (want_prune) out.pruned_units = D.h_fbuf[4];
+            if (want_prune) {
+                out.pruned_units = D.h_fbuf[4];
+                out.inplace_units = D.h_fbuf[5];
+                out.pruned_first = D.h_fbuf[6];
+            }
             if (nc > D.cand_first) {
                 more.resize(nc);
                 check(hipMemcpy(more.data(), D.d_fbuf + kFilterHeader, 8 * (size_t)nc, hipMemcpyDeviceToHost),

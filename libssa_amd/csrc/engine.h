@@ -226,6 +226,8 @@ struct SearchScores {
     // launch and how many of them were skipped; entries of a skipped unit
     // carry a lower bound of their score, below the final k-th score
     uint32_t part_units = 0, pruned_units = 0;
+    // ... the units that ran their remaining parts in place, and the skipped ones of the first part boundary
+    uint32_t inplace_units = 0, pruned_first = 0;
     int64_t get(size_t v, size_t e) const {
         const int32_t x = s32[v * entries + e];
         if (x != INT32_MIN) return x;

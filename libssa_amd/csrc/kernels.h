@@ -145,16 +145,34 @@ struct StripArgs {
 //   lock, tau, list: part 0 offers its lanes' exact maxima over its rows to
 //     the list of the k largest; tau = its smallest once full, a lower bound
 //     of the final k-th score;
-//   count: the units skipped.
+//   lock2, list2: a second list of the k largest, of exact final scores: every
+//     real, decided lane that reaches the end of its last part offers its
+//     score.  Each list holds k distinct entries at lower bounds of their final
+//     scores, so each list's smallest, and tau = the larger of the two (an
+//     atomic max: both only grow), is a lower bound of the final k-th score;
+//   count, first: the units skipped, and those of them skipped at the first
+//     part boundary;
+//   prom[2], inplace: per part boundary, the least best-lane maximum at which
+//     a unit that cannot be skipped runs its remaining parts itself, in the
+//     same workgroup (~0: never; option "prune_inplace_pct"), and how many did;
+//   inplace waves, done: the waves (holding a group) of the units that went in
+//     place, and those of them that have ended: while the two differ, a later
+//     part whose bound is not below tau yet waits, bounded, for tau's final
+//     value (the units in place are resident, so they end regardless);
+//   cut[2]: the strip index of the first and second part boundary of a plan
+//     with unequal parts (0: StripArgs::part_strips strips each).
 // Every part but the last publishes as its quad's bound the most any of the
 // quad's entries can still score below its last row i_b: max over lanes of
 // max_j H(i_b, j), plus rem.  A later part whose bound is below tau writes its
 // lanes' maxima so far as their scores and returns.
-constexpr uint32_t kPruneLock = 0, kPruneTau = 1, kPruneCount = 2, kPruneK = 3, kPruneRem = 4, kPruneList = 16,
-                   kPruneWords = kPruneList + 64;
+constexpr uint32_t kPruneLock = 0, kPruneTau = 1, kPruneCount = 2, kPruneK = 3, kPruneRem = 4, kPruneLock2 = 6,
+                   kPruneInplace = 7, kPruneFirst = 8, kPruneProm = 9, kPruneCut = 11, kPruneInplaceWaves = 13,
+                   kPruneInplaceDone = 14, kPruneList = 16,
+                   kPruneList2 = kPruneList + 64, kPruneWords = kPruneList2 + 64;
 // bound values above every score: never skip (a lane the part-0 maximum leaves
-// undecided) / an earlier part of the quad was skipped
-constexpr uint32_t kBoundNever = 0xffffffffu, kBoundSkipped = 0xfffffffeu;
+// undecided) / an earlier part of the quad was skipped / the earlier part's
+// workgroup finishes the quad in place (its later units return at once)
+constexpr uint32_t kBoundNever = 0xffffffffu, kBoundSkipped = 0xfffffffeu, kBoundInplace = 0xfffffffdu;
 
 // Long DB entries (long_kernel): the query rows split over the lanes of W
 // waves (RL consecutive rows per lane, passes of W*64*RL rows), DB columns
@@ -298,7 +316,8 @@ struct FilterArgs {
     uint32_t* pass;
     uint32_t epoch;
     // single view: the pair kernel's skipped-unit count (kPruneCount),
-    // copied into counters[4] like status; null: none
+    // copied into counters[4] like status, with kPruneInplace and kPruneFirst
+    // of the same block into counters[5] and [6]; null: none
     const uint32_t* pruned;
 };
 constexpr int kFilterSeqWord = 15;    // header word that carries FilterArgs::host_seq
@@ -457,7 +476,7 @@ struct TableArgs {
     // the pair launch's pruning block (kPrune*, before StripArgs::part_done),
     // written by block 0: k, rem, everything else 0; null: none
     uint32_t* prune_blk;
-    uint32_t prune_k, prune_rem[2];
+    uint32_t prune_k, prune_rem[2], prune_prom[2], prune_cut[2];
 };
 hipError_t launch_pair_tables(const TableArgs& a, hipStream_t st);
 // dst (device) <- src (pinned host), bytes a multiple of 4: a kernel on st

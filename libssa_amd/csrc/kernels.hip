@@ -763,7 +763,11 @@ __global__ void __launch_bounds__(256) filter_select(const FilterArgs a0) {
     const uint32_t tid = blockIdx.x * 256 + threadIdx.x;
     if (tid < a.nviews) a.counters[3 + tid] = a.ovf_count[(size_t)tid * a.ovf_stride];
     if (tid == 0 && a.status) a.counters[2] = *a.status;
-    if (tid == 0 && a.pruned) a.counters[4] = *a.pruned;
+    if (tid == 0 && a.pruned) {
+        a.counters[4] = *a.pruned;
+        a.counters[5] = a.pruned[kPruneInplace - kPruneCount];
+        a.counters[6] = a.pruned[kPruneFirst - kPruneCount];
+    }
     const uint32_t e0 = tid * kSelectPer;
     if (e0 < a.n) {
         int32_t x[kSelectPer];
@@ -969,7 +973,11 @@ __global__ void __launch_bounds__(256) filter_onepass(const FilterArgs a0) {
     if (b == 0) {
         for (uint32_t v = threadIdx.x; v < a.nviews; v += 256) a.counters[3 + v] = a.ovf_count[(size_t)v * a.ovf_stride];
         if (threadIdx.x == 0 && a.status) a.counters[2] = *a.status;
-        if (threadIdx.x == 0 && a.pruned) a.counters[4] = *a.pruned;
+        if (threadIdx.x == 0 && a.pruned) {
+            a.counters[4] = *a.pruned;
+            a.counters[5] = a.pruned[kPruneInplace - kPruneCount];
+            a.counters[6] = a.pruned[kPruneFirst - kPruneCount];
+        }
     }
 #pragma unroll
     for (int i = 0; i < MW; i++) {
@@ -1043,7 +1051,11 @@ __global__ void __launch_bounds__(256) pair_tables_kernel(const TableArgs a) {
     if (a.zero_hdr && blockIdx.x == 0 && threadIdx.x < a.nzero_hdr) a.zero_hdr[threadIdx.x] = 0;
     if (a.prune_blk && blockIdx.x == 0 && threadIdx.x < kPruneWords) {
         const uint32_t t = threadIdx.x;
-        a.prune_blk[t] = t == kPruneK ? a.prune_k : t == kPruneRem ? a.prune_rem[0] : t == kPruneRem + 1 ? a.prune_rem[1] : 0u;
+        a.prune_blk[t] = t == kPruneK ? a.prune_k
+                         : t == kPruneRem || t == kPruneRem + 1 ? a.prune_rem[t - kPruneRem]
+                         : t == kPruneProm || t == kPruneProm + 1 ? a.prune_prom[t - kPruneProm]
+                         : t == kPruneCut || t == kPruneCut + 1 ? a.prune_cut[t - kPruneCut]
+                                                                : 0u;
     }
     if (a.gate && blockIdx.x == 0 && threadIdx.x == 0) {
         // the long entries' workgroups (another stream) start first; bounded

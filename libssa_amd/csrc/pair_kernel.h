@@ -151,14 +151,19 @@ __device__ __forceinline__ void sw_emit(int32_t* scores, uint32_t* ovf_list, uin
         scores[o] = score;
     }
 }
-// The wave offers its lanes' part-0 scores sc (0: none) to the list of the k
-// largest.  Only a wave with a lane above tau takes the lock (lane 0, a
+// The wave offers its lanes' scores sc (0: none) to one of the two lists of the
+// k largest (kernels.h kPrune*): part-0 maxima to the list at kPruneList under
+// kPruneLock, exact final scores to the one at kPruneList2 under kPruneLock2.
+// tau is the larger of the two lists' minima: both only grow, so each offer
+// publishes its list's minimum with an atomic max on the one tau word.
+// Only a wave with a lane above tau takes the lock (lane 0, a
 // bounded number of tries: a wave that does not get it skips its offer, which
 // leaves tau lower and still valid).  Under the lock the list lives one slot
 // per lane; the wave's candidates replace its smallest slots, largest first.
 // Every access is an agent-scope atomic (the XCDs' L2s are not coherent), and
 // the list's stores have completed before tau's, tau's before the unlock.
-__device__ __forceinline__ void prune_offer(uint32_t* pr, uint32_t k, uint32_t sc, int lane) {
+__device__ __forceinline__ void prune_offer(uint32_t* pr, uint32_t lock, uint32_t list, uint32_t k, uint32_t sc,
+                                            int lane) {
     bool cand = false;
     uint32_t got = 0;
     for (int t = 0; t < 16; t++) {
@@ -166,8 +171,11 @@ __device__ __forceinline__ void prune_offer(uint32_t* pr, uint32_t k, uint32_t s
         cand = sc > tau;
         if (__ballot(cand) == 0) return;
         if (lane == 0) {
+            // (any value but 0 holds the lock: k, which is loaded behind the
+            // strips.  A constant is hoisted above them in a register pair with
+            // exp and spilled across the DP loop)
             uint32_t exp = 0;
-            got = __hip_atomic_compare_exchange_strong(pr + kPruneLock, &exp, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+            got = __hip_atomic_compare_exchange_strong(pr + lock, &exp, k, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                                        __HIP_MEMORY_SCOPE_AGENT) ? 1u : 0u;
         }
         got = __builtin_amdgcn_readfirstlane(got);
@@ -177,7 +185,7 @@ __device__ __forceinline__ void prune_offer(uint32_t* pr, uint32_t k, uint32_t s
     if (!got) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     uint32_t mine = (uint32_t)lane < k
-                        ? __hip_atomic_load(pr + kPruneList + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                        ? __hip_atomic_load(pr + list + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                         : 0xffffffffu;
     bool dirty = false;
     for (uint32_t it = 0; it < k; it++) {
@@ -192,14 +200,25 @@ __device__ __forceinline__ void prune_offer(uint32_t* pr, uint32_t k, uint32_t s
         const int src = __ffsll((long long)__ballot(cand && sc == c)) - 1;
         if (lane == src) cand = false;
     }
-    if (dirty) __hip_atomic_store(pr + kPruneList + lane, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (dirty) __hip_atomic_store(pr + list + lane, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t ntau = wave_min_u32(mine);      // 0 while a slot is empty
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) __hip_atomic_store(pr + kPruneTau, ntau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) (void)__hip_atomic_fetch_max(pr + kPruneTau, ntau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) __hip_atomic_store(pr + kPruneLock, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) __hip_atomic_store(pr + lock, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The kernel's argument block read again from the kernarg segment, behind an
+// opaque point: what the SW code after the strips takes from it is loaded
+// there and holds no scalar register across the DP loop (whose SGPRs are the
+// tight resource: spilled ones come back as v_readlane in the loop).
+typedef const __attribute__((address_space(4))) StripArgs strip_kargs;
+__device__ __forceinline__ strip_kargs* kernargs_again() {
+    strip_kargs* p = (strip_kargs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
 }
 
 template <int NP, bool NW, int NPT>
@@ -268,21 +287,50 @@ pair_kernel(const StripArgs a) {
                     if (done && pr[kPruneK] != 0) {
                         const uint32_t bd = __hip_atomic_load(a.part_done + 2 * (size_t)wg + 1, __ATOMIC_RELAXED,
                                                               __HIP_MEMORY_SCOPE_AGENT);
-                        const uint32_t tau = __hip_atomic_load(pr + kPruneTau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        skip = bd == kBoundSkipped || bd < tau ? 1u : 0u;
+                        uint32_t tau = __hip_atomic_load(pr + kPruneTau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (bd < kBoundInplace && bd >= tau) {
+                            // Not skippable yet -- but while units are finishing
+                            // in place, final scores are on their way into tau.
+                            // Those units are resident (they decided in a
+                            // running workgroup), so they end whatever this one
+                            // does: wait for them, bounded like the wait above,
+                            // or until tau has passed the bound.  Where the
+                            // launch fills the GPU many times over they are long
+                            // done when the deferred parts take their tickets;
+                            // where it does not, the wait costs an idle CU's time
+                            // and saves the whole rest of the unit.
+                            const uint64_t t1 = __builtin_amdgcn_s_memrealtime();
+                            while (__hip_atomic_load(pr + kPruneInplaceWaves, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) !=
+                                       __hip_atomic_load(pr + kPruneInplaceDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &&
+                                   __builtin_amdgcn_s_memrealtime() - t1 < a.part_wait) {
+                                __builtin_amdgcn_s_sleep(16);
+                                tau = __hip_atomic_load(pr + kPruneTau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                if (bd < tau) break;
+                            }
+                            tau = __hip_atomic_load(pr + kPruneTau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                        // (2: the previous part's workgroup runs this part
+                        // itself, in place -- nothing to do here)
+                        skip = bd == kBoundInplace ? 2u : bd == kBoundSkipped || bd < tau ? 1u : 0u;
                     }
                     lds[1] = skip;
                 }
             }
             __syncthreads();
-            if (!NW && __builtin_amdgcn_readfirstlane(lds[1])) {
+            const uint32_t skip = NW ? 0u : __builtin_amdgcn_readfirstlane(lds[1]);
+            if (!NW && skip) {
                 // the lanes' scores are their maxima so far, decoded as at the
-                // kernel's end; a later part of the quad is told to skip too
+                // kernel's end; a later part of the quad is told the same
+                // (skipped, or finished in place: that workgroup touches the
+                // quad's words no more, and emits the scores itself)
                 if (threadIdx.x == 0) {
-                    atomicAdd(a.part_done - kPruneWords + kPruneCount, 1u);
+                    if (skip == 1) {
+                        atomicAdd(a.part_done - kPruneWords + kPruneCount, 1u);
+                        if (part == 1) atomicAdd(a.part_done - kPruneWords + kPruneFirst, 1u);
+                    }
                     if (part + 1 < a.nparts) {
-                        __hip_atomic_store(a.part_done + 2 * (size_t)wg + 1, kBoundSkipped, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store(a.part_done + 2 * (size_t)wg + 1, skip == 2 ? kBoundInplace : kBoundSkipped,
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         __builtin_amdgcn_s_waitcnt(0);
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                         __hip_atomic_store(a.part_done + 2 * (size_t)wg, a.part_epoch + part, __ATOMIC_RELAXED,
@@ -290,7 +338,7 @@ pair_kernel(const StripArgs a) {
                     }
                 }
                 const uint32_t g = a.g_first + wg * W + wave;
-                if (part + 1 < a.nparts || g >= a.ngroups) return;
+                if (skip == 2 || part + 1 < a.nparts || g >= a.ngroups) return;
                 const uint32_t gl = g * 64 + lane;
                 const uint32_t o = a.lane_out[gl];
                 if (o == 0xffffffffu) return;
@@ -659,30 +707,53 @@ pair_kernel(const StripArgs a) {
     using TailNP = std::integral_constant<int, NPT ? NPT : 8>;
     // this unit's strips [s0, s1) of the nstrips main strips + the tail strip
     const uint32_t T = a.nstrips + (NPT > 0 ? 1u : 0u);
-    const uint32_t s0 = split ? part * a.part_strips : 0u;
-    const uint32_t s1 = split ? min(T, s0 + a.part_strips) : T;
-    for (uint32_t s = s0; s < min(s1, a.nstrips); s++) {
-        handoff = split && part + 1 < a.nparts && s + 1 == s1;
-        strip(MainNP{}, std::false_type{}, (int)s * 2 * NP, qpt + (size_t)s * prow * prow * NP);
-    }
-    if (NPT > 0 && s1 == T) {
-        handoff = false;
-        strip(TailNP{}, std::integral_constant<bool, NW>{}, (int)a.nstrips * 2 * NP, qpt_tail);
+    uint32_t s0 = split ? part * a.part_strips : 0u;
+    uint32_t s1 = split ? min(T, s0 + a.part_strips) : T;
+    if (!NW && split) {
+        // a pruned search's own part boundaries (kernels.h kPruneCut; 0: equal parts)
+        const uint32_t* const cut = a.part_done - kPruneWords + kPruneCut;
+        const uint32_t c0 = cut[0], c1 = cut[1];
+        if (c0 != 0) {
+            s0 = part == 0 ? 0u : part == 1 ? c0 : c1;
+            s1 = part == 0 ? c0 : part == 1 && a.nparts > 2 ? c1 : T;
+        }
     }
 
-    if (split && part + 1 < a.nparts) {
+    // A non-last part hands its group on behind its last strip (always a main
+    // strip).  SW: true when this workgroup runs the next part itself, in
+    // place -- part, s1 and the row buffer it writes are then the next part's.
+    auto hand_on = [&]() -> bool {
+        // (the thread index behind an opaque point: what is derived from it
+        // here -- lane masks -- is not hoisted above the strips, where it
+        // would hold scalar registers across the DP loop)
+        uint32_t tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int ln = (int)(tid & 63);
         // hand the group on: running maxima, then (after every wave's row
         // buffer stores and maxima are visible at agent scope) the part count
-        if (!NW && active) __hip_atomic_store(smax + gl, S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t* part_done = a.part_done;
+        const uint32_t* lane_out = a.lane_out;
+        uint32_t nmax16 = a.nmax16, part_epoch = a.part_epoch;
+        if constexpr (!NW) {
+            // (SW: none of these is needed before)
+            strip_kargs* const ka = kernargs_again();
+            part_done = ka->part_done;
+            lane_out = ka->lane_out;
+            nmax16 = ka->nmax16;
+            part_epoch = ka->part_epoch;
+            // (pruning and in-place work run one query: qi is 0)
+            if (active) __hip_atomic_store(ka->part_smax + (size_t)qi * ka->ngroups * 64 + gl, S, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+        }
         // top-k pruning: the wave's bound of what its entries can still score
         // below this part's last row i_b, and (part 0) its offer to tau
-        uint32_t* const pr = a.part_done - kPruneWords;
+        uint32_t* const pr = part_done - kPruneWords;
         const uint32_t pk = NW ? 0u : __builtin_amdgcn_readfirstlane(pr[kPruneK]);
         const bool prune0 = pk != 0;
-        uint32_t wbound = 0;
+        uint32_t wbound = 0, wbest = 0;
         if (prune0 && active) {
             // a lane that counts: a real entry the 16-bit patterns score exactly
-            const bool real = a.lane_out[gl] != 0xffffffffu && len != 0 && len <= a.nmax16;
+            const bool real = lane_out[gl] != 0xffffffffu && len != 0 && len <= nmax16;
             const uint32_t sc = real ? sw_score(S, Rabs) : 0u;
             // Hb = max_j H(i_b, j) over the lane's own columns, from the
             // handoff boundary row this wave just wrote (low halves; column
@@ -711,36 +782,125 @@ pair_kernel(const StripArgs a) {
             // re-scored after every part: its quad is never skipped)
             const uint32_t lb = !real ? 0u : sc == 0 ? kBoundNever : x + Rabs + pr[kPruneRem + (part == 0 ? 0 : 1)];
             wbound = wave_max_u32(lb);
+            wbest = wave_max_u32(sc);
             // (once per lane: tau is the k-th of k distinct entries)
-            if (part == 0) prune_offer(pr, pk, sc, lane);
+            if (part == 0) prune_offer(pr, kPruneLock, kPruneList, pk, sc, ln);
         }
         // every wave's device-scope stores complete, then one flag store
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __syncthreads();
+        uint32_t inplace = 0;
         if (prune0) {
-            // (the pair table is no longer read: its first dwords carry the waves' bounds)
+            // (the pair table is no longer read: its first dwords carry the waves'
+            // bounds and best maxima, then the workgroup's decision)
             // (the wave index anew: kept from the kernel's start it would be one more
             // scalar register live across the DP loop)
-            if (lane == 0) lds[2 + (threadIdx.x >> 6)] = wbound;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                uint32_t bd = 0;
-                for (int w = 0; w < W; w++) bd = max(bd, lds[2 + w]);
-                __hip_atomic_store(a.part_done + 2 * (size_t)wg + 1, bd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __builtin_amdgcn_s_waitcnt(0);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (ln == 0) {
+                lds[2 + (tid >> 6)] = wbound;
+                lds[2 + W + (tid >> 6)] = wbest;
             }
+            __syncthreads();
+            if (tid == 0) {
+                uint32_t bd = 0, best = 0;
+                for (int w = 0; w < W; w++) {
+                    bd = max(bd, lds[2 + w]);
+                    best = max(best, lds[2 + W + w]);
+                }
+                // finish in place: the unit cannot be skipped now and is
+                // promising -- its best real lane's maximum is at least the
+                // host's share (option "prune_inplace_pct") of what the rows
+                // so far can give (kPruneProm; ~0: never).  A choice of
+                // schedule only: the same cells either way.
+                const uint32_t tau = __hip_atomic_load(pr + kPruneTau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const uint32_t prom = pr[kPruneProm + (part == 0 ? 0 : 1)];
+                // A unit already in place (it reads its own sentinel: a unit
+                // that found one at its start has returned) goes through to
+                // the end and publishes nothing more -- the quad's words
+                // belong to the deferred units, which pass the sentinel on.
+                // (part 0 finds an earlier launch's word there)
+                const bool mine = part > 0 && __hip_atomic_load(part_done + 2 * (size_t)wg + 1, __ATOMIC_RELAXED,
+                                                                __HIP_MEMORY_SCOPE_AGENT) == kBoundInplace;
+                const bool go = mine || (prom != 0xffffffffu && bd >= tau && best >= prom);
+                lds[1] = mine ? 2u : go ? 1u : 0u;
+                if (!mine) {
+                    if (go) {
+                        // (and its waves that hold a group: each reports its end, kPruneInplaceDone)
+                        strip_kargs* const ka = kernargs_again();
+                        atomicAdd(pr + kPruneInplace, 1u);
+                        atomicAdd(pr + kPruneInplaceWaves, min((uint32_t)W, ka->ngroups - ka->g_first - wg * W));
+                    }
+                    __hip_atomic_store(part_done + 2 * (size_t)wg + 1, go ? kBoundInplace : bd, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+                    __builtin_amdgcn_s_waitcnt(0);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                }
+            }
+            __syncthreads();
+            inplace = __builtin_amdgcn_readfirstlane(lds[1]);
         }
-        if (threadIdx.x == 0)
-            __hip_atomic_store(a.part_done + 2 * ((size_t)wg * nqs + qi), a.part_epoch + part, __ATOMIC_RELAXED,
+        if (tid == 0 && inplace != 2)
+            __hip_atomic_store(part_done + 2 * ((size_t)wg * nqs + qi), part_epoch + part, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
-        return;
+        if (NW || !inplace) return false;
+        // the next part, here and now: its top boundary is the handoff row
+        // this workgroup just wrote (rbr, set by the strip), its own
+        // boundaries go to that part's buffer as a deferred unit's would --
+        // one buffer, one writer.  The deferred units of the quad read the
+        // sentinel and return.
+        part++;
+        if constexpr (!NW) {
+            // (the group's block anew, as a scalar: pruning runs one query, roff's qi is 0)
+            strip_kargs* const ka = kernargs_again();
+            const uint32_t blk = __builtin_amdgcn_readfirstlane(ka->groups[__builtin_amdgcn_readfirstlane(gl) >> 6].blk);
+            rbw = group_rsrc((part == 1 ? ka->rowbuf2 : ka->rowbuf3) + (size_t)blk * 256);
+            const uint32_t c1 = pr[kPruneCut] != 0 ? pr[kPruneCut + 1] : (part + 1) * ka->part_strips;
+            s1 = part + 1 < ka->nparts ? min(T, c1) : T;
+        }
+        return true;
+    };
+
+    for (uint32_t s = s0; s < min(s1, a.nstrips); s++) {
+        handoff = split && part + 1 < a.nparts && s + 1 == s1;
+        strip(MainNP{}, std::false_type{}, (int)s * 2 * NP, qpt + (size_t)s * prow * prow * NP);
+        if constexpr (!NW)
+            if (handoff && !hand_on()) return;
     }
+    if (NPT > 0 && s1 == T) {
+        handoff = false;
+        strip(TailNP{}, std::integral_constant<bool, NW>{}, (int)a.nstrips * 2 * NP, qpt_tail);
+    }
+    if constexpr (NW)
+        if (split && part + 1 < a.nparts) {
+            (void)hand_on();
+            return;
+        }
     if (!active) return;
     if (a.timeline && lane == 0)
         a.timeline[g - a.g_first] = make_uint4(g, t_start, (uint32_t)__builtin_amdgcn_s_memrealtime(), hw_place());
     const uint32_t o = a.lane_out[gl];
+    if (!NW && a.nparts > 1) {
+        // top-k pruning: every real lane whose score is final and exact here
+        // offers it to the second list (the whole wave: prune_offer)
+        strip_kargs* const ka = kernargs_again();
+        uint32_t* const pr = ka->part_done - kPruneWords;
+        const uint32_t pk = __builtin_amdgcn_readfirstlane(pr[kPruneK]);
+        if (pk != 0) {
+            const bool real = o != 0xffffffffu && len != 0 && len <= ka->nmax16;
+            prune_offer(pr, kPruneLock2, kPruneList2, pk, real ? sw_score(S, Rabs) : 0u, lane);
+            // a wave of a unit that finished in place (it still finds its own
+            // sentinel: a deferred unit that found one has returned) reports
+            // its end, behind its offer: the deferred units that wait for
+            // tau's final value count these
+            if (split && part > 0) {
+                __builtin_amdgcn_s_waitcnt(0);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                if (lane == 0 && __hip_atomic_load(ka->part_done + 2 * (size_t)wg + 1, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT) == kBoundInplace)
+                    atomicAdd(pr + kPruneInplaceDone, 1u);
+            }
+        }
+    }
     if (o == 0xffffffffu) return;
     if (len == 0) {
         scores[o] = NW ? (int32_t)(a.gap_open + (int64_t)m * a.gap_extend) : 0;
