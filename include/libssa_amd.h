@@ -113,6 +113,39 @@ typedef struct {
     char kernel[32];       /* "pairs_sw_i32" / "pairs_nw_i32" */
 } ssa_amd_pairs_stats_t;
 
+/* One pair's result of ssa_amd_align_pairs. */
+typedef struct {
+    int64_t  score;       /* what ssa_amd_score_pairs reports for the pair */
+    uint64_t region[4];   /* q begin, q end, d begin, d end -- exactly ssa_amd_align_pair's */
+    uint64_t cigar_off;   /* NUL-terminated CIGAR at cigars + cigar_off */
+    uint32_t cigar_len;
+    uint32_t flags;       /* bit 0: aligned on the host path */
+} ssa_amd_pair_alignment_t;
+
+typedef struct {
+    uint64_t pairs;        /* pairs of the last ssa_amd_align_pairs call */
+    uint64_t cells;        /* sum of qlen * dlen */
+    uint64_t host_pairs;   /* pairs aligned on the host (device_fallbacks included) */
+    uint64_t zero_pairs;   /* device SW pairs whose best score is 0: region zeros, empty CIGAR */
+    uint64_t device_fallbacks; /* device pairs a pass gave no cell for, handed to the host routine (expected 0) */
+    uint64_t dir_bytes;    /* direction bits written on the device, all chunks */
+    uint32_t groups;       /* groups of 64 pairs, one per wave */
+    uint32_t chunks;       /* pack / upload / launch / copy rounds */
+    uint32_t launches;     /* kernel launches */
+    uint32_t reserved;
+    double total_ms;       /* host wall time of the call */
+    double pack_ms;        /* host: ordering and packing, the work between two passes included */
+    double host_ms;        /* host wall time of the host path */
+    double text_ms;        /* host: runs -> CIGAR text */
+    double fwd_ms;         /* HIP-event time per pass: SW forward (the end cell) */
+    double rev_ms;         /*   SW reverse (the begin cell) */
+    double dir_ms;         /*   directions */
+    double walk_ms;        /*   the walk */
+    double kernel_ms;      /* fwd_ms + rev_ms + dir_ms + walk_ms */
+    int32_t device;        /* HIP device of the call, -1: none used */
+    char kernels[96];      /* the kernels of the call, comma-separated */
+} ssa_amd_align_pairs_stats_t;
+
 #define SSA_AMD_SW 0
 #define SSA_AMD_NW 1
 #define SSA_AMD_TOPK 0      /* sorted top-k, as sw_align/nw_align */
@@ -353,11 +386,39 @@ size_t ssa_amd_align_pair( int algo, const char * query, size_t qlen, const char
  *   "pairs_chunk" N      pairs per pack / launch round (multiples of 64); 0 (default): as many as
  *                        fit 256 MiB of device memory
  *   "pairs_host" 0|1     1: every pair on the host path (default 0)
- * Tracebacks: ssa_amd_align_pair on the pairs of interest. */
+ * Tracebacks: ssa_amd_align_pairs for a batch, ssa_amd_align_pair for one pair. */
 int ssa_amd_score_pairs( int algo, const uint8_t * q_codes, const uint64_t * q_off,
                          const uint8_t * d_codes, const uint64_t * d_off,
                          size_t npairs, int64_t * scores );
 void ssa_amd_get_pairs_stats( ssa_amd_pairs_stats_t * out );
+/* Region and CIGAR of npairs independent pairs in one call: for every pair
+ * (region, CIGAR) is exactly what ssa_amd_align_pair returns for it under the
+ * current matrix and gap penalties -- a zero-score SW pair gives (0, 0, 0, 0)
+ * and an empty CIGAR, an empty side whatever that routine yields -- and score
+ * is what ssa_amd_score_pairs reports.  Arguments and their checks are
+ * ssa_amd_score_pairs'; non-zero (nothing written, nothing launched) also for
+ * a cigar_cap below the bound.
+ * The CIGAR buffer: a CIGAR's text is never longer than its operation count,
+ * which is at most qlen + dlen, so cigar_cap must be at least the sum over all
+ * pairs of (qlen_i + dlen_i + 1).  Pair i's text starts at cigars +
+ * out[i].cigar_off, is out[i].cigar_len characters long and NUL-terminated;
+ * texts do not overlap.
+ * A pair is aligned on the device under ssa_amd_score_pairs' conditions and
+ * three more: for SW a symmetric matrix (the reference's region passes score
+ * M[query][db], its direction pass M[db][query]); both lengths below 65 535
+ * (cell positions travel as 16 + 16 bits); direction bits (2 per cell) of at
+ * most 512 MiB for the pair alone.  Everything else, and every pair when no
+ * HIP device is visible, goes through ssa_amd_align_pair's routine on the
+ * host, in parallel (set_thread_count); flags bit 0 marks those.  On the
+ * device a chunk of groups runs four kernels -- SW forward (the end cell), SW
+ * reverse (the begin cell), directions, walk; NW the last two -- with the
+ * direction bits kept in device memory: a chunk holds at most 1 GiB, of which
+ * they are the largest part (ssa_amd_align_pairs_stats_t::dir_bytes).
+ * Options "pairs_chunk" and "pairs_host" apply as for ssa_amd_score_pairs. */
+int ssa_amd_align_pairs( int algo, const uint8_t * q_codes, const uint64_t * q_off,
+                         const uint8_t * d_codes, const uint64_t * d_off, size_t npairs,
+                         ssa_amd_pair_alignment_t * out, char * cigars, size_t cigar_cap );
+void ssa_amd_get_align_pairs_stats( ssa_amd_align_pairs_stats_t * out );
 /* ASCII -> DB-side residue codes of the current symbol type (us_map_sequence:
  * unknown -> 0); writes min(len, cap) codes, returns len. */
 size_t ssa_amd_map_residues( const char * ascii, size_t len, char * out, size_t cap );

@@ -83,9 +83,23 @@ class ssa_amd_pairs_stats_t(Structure):
                 ("device", c_int32), ("kernel", ctypes.c_char * 32)]
 
 
+class ssa_amd_pair_alignment_t(Structure):
+    _fields_ = [("score", c_int64), ("region", c_uint64 * 4), ("cigar_off", c_uint64), ("cigar_len", c_uint32),
+                ("flags", c_uint32)]
+
+
+class ssa_amd_align_pairs_stats_t(Structure):
+    _fields_ = [("pairs", c_uint64), ("cells", c_uint64), ("host_pairs", c_uint64), ("zero_pairs", c_uint64),
+                ("device_fallbacks", c_uint64), ("dir_bytes", c_uint64), ("groups", c_uint32), ("chunks", c_uint32),
+                ("launches", c_uint32), ("reserved", c_uint32), ("total_ms", c_double), ("pack_ms", c_double),
+                ("host_ms", c_double), ("text_ms", c_double), ("fwd_ms", c_double), ("rev_ms", c_double),
+                ("dir_ms", c_double), ("walk_ms", c_double), ("kernel_ms", c_double), ("device", c_int32),
+                ("kernels", ctypes.c_char * 96)]
+
+
 assert ctypes.sizeof(db_seq_t) == 32 and ctypes.sizeof(q_seq_t) == 24
 assert ctypes.sizeof(alignment_t) == 112 and ctypes.sizeof(alignment_list_t) == 16
-assert ctypes.sizeof(ssa_hit_t) == 24
+assert ctypes.sizeof(ssa_hit_t) == 24 and ctypes.sizeof(ssa_amd_pair_alignment_t) == 56
 
 # every symbol include/*.h declares (checked by tests/test_abi.py)
 EXPORTS = {
@@ -100,7 +114,7 @@ EXPORTS = {
                       "ssa_amd_dist_finalize", "ssa_amd_gather_logs", "ssa_amd_merge_logs", "ssa_amd_get_timeline",
                       "ssa_amd_dist_available", "ssa_amd_dist_init_fake", "ssa_amd_dist_ranks", "ssa_amd_shard_bounds",
                       "ssa_amd_get_devices", "ssa_amd_score_pairs", "ssa_amd_get_pairs_stats",
-                      "ssa_amd_map_residues"],
+                      "ssa_amd_map_residues", "ssa_amd_align_pairs", "ssa_amd_get_align_pairs_stats"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -152,6 +166,9 @@ def load():
         "ssa_amd_dist_ranks": ([], c_int),
         "ssa_amd_score_pairs": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
         "ssa_amd_get_pairs_stats": ([POINTER(ssa_amd_pairs_stats_t)], None),
+        "ssa_amd_align_pairs": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                 c_size_t], c_int),
+        "ssa_amd_get_align_pairs_stats": ([POINTER(ssa_amd_align_pairs_stats_t)], None),
         "ssa_amd_map_residues": ([c_char_p, c_size_t, c_char_p, c_size_t], c_size_t),
         "ssa_amd_shard_bounds": ([c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_size_t)], c_int),
     }
@@ -417,6 +434,60 @@ def pairs_stats():
     load().ssa_amd_get_pairs_stats(ctypes.byref(s))
     d = {f: getattr(s, f) for f, _ in ssa_amd_pairs_stats_t._fields_}
     d["kernel"] = d["kernel"].decode()
+    return d
+
+
+def align_pairs(algo, queries, targets):
+    """ssa_amd_align_pairs: [(score, (q_begin, q_end, d_begin, d_end), cigar)]
+    of queries[i] against targets[i] (two equal-length lists of uint8
+    residue-code arrays); region and CIGAR are align_pair's, the score is
+    score_pairs'.  Raises ValueError when the library refuses the arguments."""
+    if len(queries) != len(targets):
+        raise ValueError("align_pairs: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    out, text = align_pairs_flat(algo, q, qo, d, do)
+    raw = text.tobytes()
+    return [(int(o["score"]), tuple(int(x) for x in o["region"]),
+             raw[int(o["cigar_off"]):int(o["cigar_off"]) + int(o["cigar_len"])].decode()) for o in out]
+
+
+ALIGNMENT_DTYPE = [("score", "<i8"), ("region", "<u8", (4,)), ("cigar_off", "<u8"), ("cigar_len", "<u4"),
+                   ("flags", "<u4")]
+
+
+def align_pairs_flat(algo, q_codes, q_off, d_codes, d_off):
+    """ssa_amd_align_pairs on the C layout itself (the arrays of
+    score_pairs_flat): returns (out, cigars) -- a structured array of
+    ssa_amd_pair_alignment_t records (ALIGNMENT_DTYPE) and the uint8 CIGAR
+    buffer of sum(qlen + dlen + 1) bytes that out's cigar_off / cigar_len
+    index."""
+    import numpy as np
+    for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
+        if a.dtype != t or not a.flags.c_contiguous:
+            raise ValueError("align_pairs_flat: contiguous uint8 codes and uint64 offsets expected")
+    if len(q_off) != len(d_off) or len(q_off) < 1:
+        raise ValueError("align_pairs_flat: offset arrays of npairs + 1 entries expected")
+    n = len(q_off) - 1
+    out = np.zeros(n, np.dtype(ALIGNMENT_DTYPE))
+    assert out.dtype.itemsize == ctypes.sizeof(ssa_amd_pair_alignment_t)
+    cap = 1
+    if n and q_off[n] >= q_off[0] and d_off[n] >= d_off[0]:
+        cap = int(q_off[n] - q_off[0]) + int(d_off[n] - d_off[0]) + n
+    cigars = np.zeros(cap, np.uint8)
+    rc = load().ssa_amd_align_pairs(algo, q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data,
+                                    d_off.ctypes.data, n, out.ctypes.data, cigars.ctypes.data, cap)
+    if rc != 0:
+        raise ValueError(f"ssa_amd_align_pairs refused its arguments ({rc})")
+    return out, cigars
+
+
+def align_pairs_stats():
+    """ssa_amd_get_align_pairs_stats: the last align_pairs call as a dict."""
+    s = ssa_amd_align_pairs_stats_t()
+    load().ssa_amd_get_align_pairs_stats(ctypes.byref(s))
+    d = {f: getattr(s, f) for f, _ in ssa_amd_align_pairs_stats_t._fields_}
+    d["kernels"] = d["kernels"].decode()
     return d
 
 

@@ -196,5 +196,9 @@ void compute_alignments(p_alignment_list L, int algo);
 int score_pairs(int algo, const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off,
                 size_t npairs, int64_t* scores);
 const ssa_amd_pairs_stats_t& pairs_stats();
+// pairs_align.cpp: ssa_amd_align_pairs and its statistics
+int align_pairs(int algo, const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off,
+                size_t npairs, ssa_amd_pair_alignment_t* out, char* cigars, size_t cigar_cap);
+const ssa_amd_align_pairs_stats_t& align_pairs_stats();
 
 }  // namespace ssa

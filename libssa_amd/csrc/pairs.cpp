@@ -14,33 +14,9 @@
 
 #include "engine.h"
 #include "pairs.h"
+#include "pairs_align.h"   // parallel_ranges, interleave: shared with the batch aligner
 
 namespace ssa {
-
-namespace {
-
-ssa_amd_pairs_stats_t g_stats;
-
-// ------------------------------------------------------------ host workers
-// fn(begin, end) over [0, n) in ranges of `grain` items that the workers take
-// from a shared counter (the items are sorted by size, so equal contiguous
-// shares would not be equal work).  set_thread_count gives the worker count;
-// by default the machine's cores, at most 16.
-template <class F>
-void parallel_ranges(size_t n, size_t grain, F fn) {
-    grain = std::max<size_t>(grain, 1);
-    size_t workers = cfg().thread_count ? cfg().thread_count
-                                        : std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency()));
-    workers = std::max<size_t>(1, std::min(workers, (n + grain - 1) / grain));
-    std::atomic<size_t> next{0};
-    auto work = [&]() {
-        for (size_t b; (b = next.fetch_add(grain)) < n;) fn(b, std::min(n, b + grain));
-    };
-    std::vector<std::thread> pool;
-    for (size_t w = 1; w < workers; w++) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-}
 
 // ------------------------------------------------------- exact host scoring
 // The reference's 64-bit recurrences (smith_waterman_64.c / needleman_wunsch_64.c),
@@ -92,6 +68,10 @@ int64_t host_nw(const uint8_t* d, size_t dn, const uint8_t* q, size_t qn, const 
     }
     return he[2 * qn - 2];
 }
+
+namespace {
+
+ssa_amd_pairs_stats_t g_stats;
 
 // ------------------------------------------------------------ device state
 // Buffers are kept between calls and only ever grow.
@@ -171,19 +151,17 @@ size_t group_bytes(uint32_t ncb, uint32_t nstrips) {
     return (size_t)ncb * 256 + (size_t)nstrips * 2 * 256 + (size_t)ncb * 4 * 512 + 64 * 8 + 64 * 4 + sizeof(PairsGroup);
 }
 
-// One lane's codes into its column of a lane-interleaved block: 4 codes per
-// dword, consecutive dwords 256 B apart (dst = the lane's first dword; the
-// block is already filled with the padding code).
-void interleave(uint8_t* dst, const uint8_t* src, uint32_t n) {
-    uint32_t i = 0;
-    for (; i + 4 <= n; i += 4) memcpy(dst + (size_t)(i / 4) * 256, src + i, 4);
-    for (; i < n; i++) dst[(size_t)(i / 4) * 256 + (i & 3)] = src[i];
-}
-
 // automatic chunk size: device bytes of one chunk (residues, boundary buffer, results)
 constexpr size_t kChunkBudget = (size_t)256 << 20;
 
 }  // namespace
+
+bool pairs_use_device(int* device, hipStream_t* stream) {
+    if (!use_device()) return false;
+    *device = g_dev.device;
+    *stream = g_dev.stream;
+    return true;
+}
 
 const ssa_amd_pairs_stats_t& pairs_stats() {
     g_stats.strip_rows = kPairsRows;
