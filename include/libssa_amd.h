@@ -438,6 +438,59 @@ size_t ssa_amd_query_views( p_query query, q_seq_t * out, size_t cap );
 size_t ssa_amd_translate( int db_side, const char * nt_codes, size_t len, int strand, int frame,
                           char * out, size_t cap );
 
+/* Ends-free (semi-global) alignment of a batch of pairs: NW's recurrence
+ * (rows = q side, columns = d side, scores M[d][q], a gap of length L costs
+ * gap_open + L * gap_extend) in which each of the four sequence ends may be
+ * free.  `ends` is a mask of: */
+#define SSA_AMD_FREE_Q_BEGIN 1   /* the alignment may start anywhere in q: H(i, -1) = 0 */
+#define SSA_AMD_FREE_Q_END   2   /* ... and end anywhere in q: candidates (i, dlen - 1) for every i */
+#define SSA_AMD_FREE_D_BEGIN 4   /* the alignment may start anywhere in d: H(-1, j) = 0 */
+#define SSA_AMD_FREE_D_END   8   /* ... and end anywhere in d: candidates (qlen - 1, j) for every j */
+/* Mask 0 is NW's score; 15 is the overlap alignment; FREE_Q_BEGIN | FREE_Q_END
+ * places d (a read) globally inside q (a window), FREE_D_BEGIN | FREE_D_END the
+ * other way round.  The end cell is the candidate with the greatest H -- the
+ * corner (qlen - 1, dlen - 1) is always one -- and among equal candidates the
+ * one with the greatest (d_end, q_end) in lexicographic order; the score is
+ * its H.  An empty side: 0 when both sides are empty or the other side has a
+ * free begin or end, else gap_open + L * gap_extend over the other side's
+ * length L.
+ * ssa_amd_score_pairs_ends: arguments, their checks, return codes, options
+ * ("pairs_chunk", "pairs_host"), device choice and host path are
+ * ssa_amd_score_pairs'; an `ends` outside 0..15 also returns non-zero (nothing
+ * written, nothing launched).  The call reports through
+ * ssa_amd_get_pairs_stats with kernel "pairs_ends_i32". */
+int ssa_amd_score_pairs_ends( int ends, const uint8_t * q_codes, const uint64_t * q_off,
+                              const uint8_t * d_codes, const uint64_t * d_off,
+                              size_t npairs, int64_t * scores );
+/* Region and CIGAR of the same alignments; arguments, checks, the CIGAR
+ * buffer and its bound are ssa_amd_align_pairs'.  score is what
+ * ssa_amd_score_pairs_ends reports; region = {q begin, q end, d begin, d end},
+ * inclusive, ends at the end cell above.  Direction bits are derived as
+ * ssa_amd_align_pair derives them for NW, under the ends-free boundaries; the
+ * walk goes from the end cell until it leaves the matrix, left first ('I', a
+ * target residue), then up ('D', a query residue), else diagonal ('M'), and --
+ * unlike ssa_amd_align_pair's -- reads a cell's gap-extension bits only when
+ * it entered the cell through that gap, so that the text re-scores exactly.
+ * Unlike NW's, the CIGAR also accounts for the whole region: where
+ * the walk leaves through column -1 at row i, a free q begin starts the
+ * region at q begin = i + 1, else q begin = 0 and a run of i + 1 D leads the
+ * text; the same through row -1 with the d begin and I.  So M adds M[d][q],
+ * a run of L adds gap_open + L * gap_extend, and the text re-scored from
+ * (q begin, d begin) gives the score and ends at (q end + 1, d end + 1).  An
+ * empty side gives region zeros and an empty CIGAR.
+ * A pair is aligned on the device under ssa_amd_align_pairs' NW conditions
+ * (an int8 matrix, penalties <= 0, the score bound, both lengths below
+ * 65 535, direction bits -- four per cell here -- of at most 512 MiB for the
+ * pair; no symmetry needed): one sweep writes direction bits, score and end
+ * cell, the walk follows on the device; a chunk holds at most 2 GiB.
+ * Everything else goes through the int64 host routine; flags bit 0 marks
+ * those.  The call reports through
+ * ssa_amd_get_align_pairs_stats: kernels "pairs_ends_dir,pairs_ends_walk"
+ * (empty when nothing was launched), fwd_ms = rev_ms = 0, zero_pairs = 0. */
+int ssa_amd_align_pairs_ends( int ends, const uint8_t * q_codes, const uint64_t * q_off,
+                              const uint8_t * d_codes, const uint64_t * d_off, size_t npairs,
+                              ssa_amd_pair_alignment_t * out, char * cigars, size_t cigar_cap );
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,7 +114,8 @@ EXPORTS = {
                       "ssa_amd_dist_finalize", "ssa_amd_gather_logs", "ssa_amd_merge_logs", "ssa_amd_get_timeline",
                       "ssa_amd_dist_available", "ssa_amd_dist_init_fake", "ssa_amd_dist_ranks", "ssa_amd_shard_bounds",
                       "ssa_amd_get_devices", "ssa_amd_score_pairs", "ssa_amd_get_pairs_stats",
-                      "ssa_amd_map_residues", "ssa_amd_align_pairs", "ssa_amd_get_align_pairs_stats"],
+                      "ssa_amd_map_residues", "ssa_amd_align_pairs", "ssa_amd_get_align_pairs_stats",
+                      "ssa_amd_score_pairs_ends", "ssa_amd_align_pairs_ends"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -169,6 +170,9 @@ def load():
         "ssa_amd_align_pairs": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                                  c_size_t], c_int),
         "ssa_amd_get_align_pairs_stats": ([POINTER(ssa_amd_align_pairs_stats_t)], None),
+        "ssa_amd_score_pairs_ends": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+        "ssa_amd_align_pairs_ends": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                      c_size_t], c_int),
         "ssa_amd_map_residues": ([c_char_p, c_size_t, c_char_p, c_size_t], c_size_t),
         "ssa_amd_shard_bounds": ([c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_size_t)], c_int),
     }
@@ -413,18 +417,22 @@ def score_pairs_flat(algo, q_codes, q_off, d_codes, d_off):
     """ssa_amd_score_pairs on the C layout itself: contiguous uint8 code
     arrays and uint64 offset arrays of npairs + 1 entries each (no per-call
     concatenation: what a caller with many pairs keeps around)."""
+    return _score_flat("ssa_amd_score_pairs", "score_pairs_flat", algo, q_codes, q_off, d_codes, d_off)
+
+
+def _score_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off):
     import numpy as np
     for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
         if a.dtype != t or not a.flags.c_contiguous:
-            raise ValueError("score_pairs_flat: contiguous uint8 codes and uint64 offsets expected")
+            raise ValueError(f"{name}: contiguous uint8 codes and uint64 offsets expected")
     if len(q_off) != len(d_off) or len(q_off) < 1:
-        raise ValueError("score_pairs_flat: offset arrays of npairs + 1 entries expected")
+        raise ValueError(f"{name}: offset arrays of npairs + 1 entries expected")
     n = len(q_off) - 1
     out = np.zeros(n, np.int64)
-    rc = load().ssa_amd_score_pairs(algo, q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data,
-                                    d_off.ctypes.data, n, out.ctypes.data)
+    rc = getattr(load(), symbol)(mode, q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data,
+                                 d_off.ctypes.data, n, out.ctypes.data)
     if rc != 0:
-        raise ValueError(f"ssa_amd_score_pairs refused its arguments ({rc})")
+        raise ValueError(f"{symbol} refused its arguments ({rc})")
     return out
 
 
@@ -446,10 +454,7 @@ def align_pairs(algo, queries, targets):
         raise ValueError("align_pairs: queries and targets differ in length")
     q, qo = _concat_codes(queries)
     d, do = _concat_codes(targets)
-    out, text = align_pairs_flat(algo, q, qo, d, do)
-    raw = text.tobytes()
-    return [(int(o["score"]), tuple(int(x) for x in o["region"]),
-             raw[int(o["cigar_off"]):int(o["cigar_off"]) + int(o["cigar_len"])].decode()) for o in out]
+    return _alignment_list(*align_pairs_flat(algo, q, qo, d, do))
 
 
 ALIGNMENT_DTYPE = [("score", "<i8"), ("region", "<u8", (4,)), ("cigar_off", "<u8"), ("cigar_len", "<u4"),
@@ -462,12 +467,16 @@ def align_pairs_flat(algo, q_codes, q_off, d_codes, d_off):
     ssa_amd_pair_alignment_t records (ALIGNMENT_DTYPE) and the uint8 CIGAR
     buffer of sum(qlen + dlen + 1) bytes that out's cigar_off / cigar_len
     index."""
+    return _align_flat("ssa_amd_align_pairs", "align_pairs_flat", algo, q_codes, q_off, d_codes, d_off)
+
+
+def _align_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off):
     import numpy as np
     for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
         if a.dtype != t or not a.flags.c_contiguous:
-            raise ValueError("align_pairs_flat: contiguous uint8 codes and uint64 offsets expected")
+            raise ValueError(f"{name}: contiguous uint8 codes and uint64 offsets expected")
     if len(q_off) != len(d_off) or len(q_off) < 1:
-        raise ValueError("align_pairs_flat: offset arrays of npairs + 1 entries expected")
+        raise ValueError(f"{name}: offset arrays of npairs + 1 entries expected")
     n = len(q_off) - 1
     out = np.zeros(n, np.dtype(ALIGNMENT_DTYPE))
     assert out.dtype.itemsize == ctypes.sizeof(ssa_amd_pair_alignment_t)
@@ -475,11 +484,54 @@ def align_pairs_flat(algo, q_codes, q_off, d_codes, d_off):
     if n and q_off[n] >= q_off[0] and d_off[n] >= d_off[0]:
         cap = int(q_off[n] - q_off[0]) + int(d_off[n] - d_off[0]) + n
     cigars = np.zeros(cap, np.uint8)
-    rc = load().ssa_amd_align_pairs(algo, q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data,
-                                    d_off.ctypes.data, n, out.ctypes.data, cigars.ctypes.data, cap)
+    rc = getattr(load(), symbol)(mode, q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data,
+                                 d_off.ctypes.data, n, out.ctypes.data, cigars.ctypes.data, cap)
     if rc != 0:
-        raise ValueError(f"ssa_amd_align_pairs refused its arguments ({rc})")
+        raise ValueError(f"{symbol} refused its arguments ({rc})")
     return out, cigars
+
+
+def _alignment_list(out, text):
+    raw = text.tobytes()
+    return [(int(o["score"]), tuple(int(x) for x in o["region"]),
+             raw[int(o["cigar_off"]):int(o["cigar_off"]) + int(o["cigar_len"])].decode()) for o in out]
+
+
+# ends-free (semi-global) alignment: the mask bits of ssa_amd_*_pairs_ends
+FREE_Q_BEGIN, FREE_Q_END, FREE_D_BEGIN, FREE_D_END = 1, 2, 4, 8
+
+
+def score_pairs_ends(ends, queries, targets):
+    """ssa_amd_score_pairs_ends: the ends-free score of queries[i] against
+    targets[i] under the mask `ends` (FREE_* bits) as an int64 array; lists
+    as score_pairs takes them.  Raises ValueError when the library refuses
+    the arguments (a mask outside 0..15 among them)."""
+    if len(queries) != len(targets):
+        raise ValueError("score_pairs_ends: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    return score_pairs_ends_flat(ends, q, qo, d, do)
+
+
+def score_pairs_ends_flat(ends, q_codes, q_off, d_codes, d_off):
+    """ssa_amd_score_pairs_ends on the C layout itself (score_pairs_flat's arrays)."""
+    return _score_flat("ssa_amd_score_pairs_ends", "score_pairs_ends_flat", ends, q_codes, q_off, d_codes, d_off)
+
+
+def align_pairs_ends(ends, queries, targets):
+    """ssa_amd_align_pairs_ends: [(score, (q_begin, q_end, d_begin, d_end),
+    cigar)] of queries[i] against targets[i] under the mask `ends`; shapes
+    and errors as align_pairs."""
+    if len(queries) != len(targets):
+        raise ValueError("align_pairs_ends: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    return _alignment_list(*align_pairs_ends_flat(ends, q, qo, d, do))
+
+
+def align_pairs_ends_flat(ends, q_codes, q_off, d_codes, d_off):
+    """ssa_amd_align_pairs_ends on the C layout itself: (out, cigars) as align_pairs_flat."""
+    return _align_flat("ssa_amd_align_pairs_ends", "align_pairs_ends_flat", ends, q_codes, q_off, d_codes, d_off)
 
 
 def align_pairs_stats():

@@ -200,5 +200,14 @@ const ssa_amd_pairs_stats_t& pairs_stats();
 int align_pairs(int algo, const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off,
                 size_t npairs, ssa_amd_pair_alignment_t* out, char* cigars, size_t cigar_cap);
 const ssa_amd_align_pairs_stats_t& align_pairs_stats();
+// pairs_ends.cpp: ssa_amd_score_pairs_ends / ssa_amd_align_pairs_ends; they report through the two
+// statistics above (set_*: pairs.cpp, pairs_align.cpp)
+int score_pairs_ends(int ends, const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes,
+                     const uint64_t* d_off, size_t npairs, int64_t* scores);
+int align_pairs_ends(int ends, const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes,
+                     const uint64_t* d_off, size_t npairs, ssa_amd_pair_alignment_t* out, char* cigars,
+                     size_t cigar_cap);
+void set_pairs_stats(const ssa_amd_pairs_stats_t& s);
+void set_align_pairs_stats(const ssa_amd_align_pairs_stats_t& s);
 
 }  // namespace ssa

@@ -168,6 +168,8 @@ const ssa_amd_pairs_stats_t& pairs_stats() {
     return g_stats;
 }
 
+void set_pairs_stats(const ssa_amd_pairs_stats_t& s) { g_stats = s; }
+
 int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff, size_t n,
                 int64_t* scores) {
     const double t0 = now_ms();

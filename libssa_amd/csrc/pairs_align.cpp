@@ -13,8 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "engine.h"
-#include "pairs_align.h"
+#include "pairs_host.h"
 
 namespace ssa {
 
@@ -22,34 +21,14 @@ namespace {
 
 ssa_amd_align_pairs_stats_t g_stats;
 
-constexpr size_t kAlign = 256;
-size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-
 // Device bytes of one chunk.  The direction bits dominate: a group costs
 // nstrips * ncb * 512 B of them (64 pairs of 390 x 513: 3.2 MB), against
 // 256 MiB for a whole chunk of ssa_amd_score_pairs; each chunk costs two host
 // round trips, so the budget is larger here.
 constexpr size_t kChunkBudget = (size_t)1 << 30;
 
-// A device buffer and (optionally) its pinned host twin; kept between calls, only ever grows.
-struct Buf {
-    uint8_t* d = nullptr;
-    uint8_t* h = nullptr;
-    size_t cap = 0;
-    void need(size_t bytes, bool host, const char* what) {
-        if (cap >= bytes && d) return;
-        release();
-        cap = bytes + bytes / 4 + kAlign;
-        check(hipMalloc((void**)&d, cap), what);
-        if (host) check(hipHostMalloc((void**)&h, cap, hipHostMallocDefault), what);
-    }
-    void release() {
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-        d = h = nullptr;
-        cap = 0;
-    }
-};
+using Buf = PairsBuf;
+inline size_t align_up(size_t x) { return pairs_align_up(x); }
 
 struct AlignDevice {
     int device = -1;
@@ -73,27 +52,10 @@ void host_align(bool nw, const uint8_t* q, size_t ql, const uint8_t* d, size_t d
     o.flags = 1;
 }
 
-// runs in traceback order -> "<count><op>" from the alignment's begin, a count of 1 omitted
-uint32_t format_runs(const uint32_t* runs, uint32_t n, char* text) {
-    static const char ops[4] = {'M', 'I', 'D', '?'};
-    char* p = text;
-    for (uint32_t r = n; r-- > 0;) {
-        uint32_t cnt = runs[r] >> 2;
-        if (cnt > 1) {
-            char tmp[12];
-            int k = 0;
-            for (; cnt; cnt /= 10) tmp[k++] = (char)('0' + cnt % 10);
-            while (k) *p++ = tmp[--k];
-        }
-        *p++ = ops[runs[r] & 3];
-    }
-    *p = 0;
-    return (uint32_t)(p - text);
-}
-
 }  // namespace
 
 const ssa_amd_align_pairs_stats_t& align_pairs_stats() { return g_stats; }
+void set_align_pairs_stats(const ssa_amd_align_pairs_stats_t& s) { g_stats = s; }
 
 int align_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff, size_t n,
                 ssa_amd_pair_alignment_t* out, char* cigars, size_t cigar_cap) {
