@@ -491,6 +491,59 @@ int ssa_amd_align_pairs_ends( int ends, const uint8_t * q_codes, const uint64_t 
                               const uint8_t * d_codes, const uint64_t * d_off, size_t npairs,
                               ssa_amd_pair_alignment_t * out, char * cigars, size_t cigar_cap );
 
+/* Banded ends-free alignment of a batch of pairs: the recurrence above,
+ * restricted pair by pair to a band of diagonals.  With i the q (row) index
+ * and j the d (column) index, pair p's band is the set of diagonals k = j - i
+ * with band_lo[p] <= k <= band_hi[p].  A cell (i, j), -1 <= i < qlen and
+ * -1 <= j < dlen, EXISTS iff its diagonal is in the band; a boundary cell
+ * (row -1 or column -1) whose begin is not free must also have diagonal 0 in
+ * the band, because its value gap_open + L * gap_extend is a gap that starts
+ * at (-1, -1).  H, E and F of a cell that does not exist are minus infinity.
+ * Everything else -- boundaries, candidates, the rule among equal candidates --
+ * is the ends-free definition over existing cells.  A band with lo <= -qlen
+ * and hi >= dlen gives exactly ssa_amd_score_pairs_ends' score and
+ * ssa_amd_align_pairs_ends' region and CIGAR text, for every mask.
+ * A band is VALID iff lo <= hi, [lo, hi] meets the diagonals an alignment may
+ * start on, [FREE_Q_BEGIN ? -qlen : 0, FREE_D_BEGIN ? dlen : 0], and meets those
+ * it may end on, [FREE_D_END ? -(qlen - 1) : dlen - qlen,
+ * FREE_Q_END ? dlen - 1 : dlen - qlen]: exactly then the best banded score is
+ * finite.  A pair of two non-empty sides with an invalid band makes the call
+ * return non-zero (nothing written, nothing launched), so no result ever
+ * means "no alignment".  A pair with an empty side ignores its band and gets
+ * the ends-free closed form.  Band values beyond [-qlen, dlen] are legal and
+ * equivalent to the clamped ones (lo = min(0, dlen - qlen) - w, hi = max(0,
+ * dlen - qlen) + w is the band of half-width w around both corners'
+ * diagonals, valid for every mask).
+ * ssa_amd_score_pairs_banded: `ends` is the mask, 0..15; the other arguments,
+ * their checks, return codes, options ("pairs_chunk", "pairs_host") and
+ * device choice are ssa_amd_score_pairs_ends'; band_lo / band_hi NULL with
+ * npairs > 0 also returns non-zero.  The call reports through
+ * ssa_amd_get_pairs_stats with kernel "pairs_banded_i32"; swept_cells counts
+ * the cells of the column blocks the waves swept, which follow the bands. */
+int ssa_amd_score_pairs_banded( int ends, const int64_t * band_lo, const int64_t * band_hi,
+                                const uint8_t * q_codes, const uint64_t * q_off,
+                                const uint8_t * d_codes, const uint64_t * d_off,
+                                size_t npairs, int64_t * scores );
+/* Region and CIGAR of the same alignments, by ssa_amd_align_pairs_ends' walk
+ * and contract: the text re-scored from (q begin, d begin) gives the score and
+ * ends at (q end + 1, d end + 1); in addition every cell it visits lies in the
+ * band.  The CIGAR buffer and its bound are ssa_amd_align_pairs'.
+ * A pair is aligned on the device under ssa_amd_align_pairs_ends' conditions,
+ * with the direction bits counted for the band alone: both lengths below
+ * 65 535 and banded bits of at most 512 MiB for the pair, so long pairs with
+ * narrow bands are device pairs.  Direction bits are kept only for the swept
+ * column blocks (ssa_amd_align_pairs_stats_t::dir_bytes); a walk that ever
+ * stood outside them would hand its pair to the host routine
+ * (device_fallbacks, expected 0).  Everything else goes through the int64 host
+ * routine, which keeps its matrices for the band only; flags bit 0 marks
+ * those.  The call reports through ssa_amd_get_align_pairs_stats: kernels
+ * "pairs_banded_dir,pairs_banded_walk" (empty when nothing was launched),
+ * fwd_ms = rev_ms = 0, zero_pairs = 0. */
+int ssa_amd_align_pairs_banded( int ends, const int64_t * band_lo, const int64_t * band_hi,
+                                const uint8_t * q_codes, const uint64_t * q_off,
+                                const uint8_t * d_codes, const uint64_t * d_off, size_t npairs,
+                                ssa_amd_pair_alignment_t * out, char * cigars, size_t cigar_cap );
+
 #ifdef __cplusplus
 }
 #endif

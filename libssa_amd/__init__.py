@@ -115,7 +115,8 @@ EXPORTS = {
                       "ssa_amd_dist_available", "ssa_amd_dist_init_fake", "ssa_amd_dist_ranks", "ssa_amd_shard_bounds",
                       "ssa_amd_get_devices", "ssa_amd_score_pairs", "ssa_amd_get_pairs_stats",
                       "ssa_amd_map_residues", "ssa_amd_align_pairs", "ssa_amd_get_align_pairs_stats",
-                      "ssa_amd_score_pairs_ends", "ssa_amd_align_pairs_ends"],
+                      "ssa_amd_score_pairs_ends", "ssa_amd_align_pairs_ends",
+                      "ssa_amd_score_pairs_banded", "ssa_amd_align_pairs_banded"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -173,6 +174,10 @@ def load():
         "ssa_amd_score_pairs_ends": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
         "ssa_amd_align_pairs_ends": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                                       c_size_t], c_int),
+        "ssa_amd_score_pairs_banded": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                        c_void_p], c_int),
+        "ssa_amd_align_pairs_banded": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                        c_void_p, c_void_p, c_size_t], c_int),
         "ssa_amd_map_residues": ([c_char_p, c_size_t, c_char_p, c_size_t], c_size_t),
         "ssa_amd_shard_bounds": ([c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_size_t)], c_int),
     }
@@ -420,7 +425,18 @@ def score_pairs_flat(algo, q_codes, q_off, d_codes, d_off):
     return _score_flat("ssa_amd_score_pairs", "score_pairs_flat", algo, q_codes, q_off, d_codes, d_off)
 
 
-def _score_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off):
+def _band_arrays(name, band, n):
+    """(band_lo, band_hi) as contiguous int64 arrays of n entries, or None for an unbanded call."""
+    import numpy as np
+    if band is None:
+        return ()
+    lo, hi = (np.ascontiguousarray(b, np.int64) for b in band)
+    if lo.shape != (n,) or hi.shape != (n,):
+        raise ValueError(f"{name}: band_lo and band_hi of npairs entries expected")
+    return lo, hi
+
+
+def _score_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band=None):
     import numpy as np
     for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
         if a.dtype != t or not a.flags.c_contiguous:
@@ -429,8 +445,9 @@ def _score_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off):
         raise ValueError(f"{name}: offset arrays of npairs + 1 entries expected")
     n = len(q_off) - 1
     out = np.zeros(n, np.int64)
-    rc = getattr(load(), symbol)(mode, q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data,
-                                 d_off.ctypes.data, n, out.ctypes.data)
+    band = _band_arrays(name, band, n)
+    rc = getattr(load(), symbol)(mode, *(b.ctypes.data for b in band), q_codes.ctypes.data, q_off.ctypes.data,
+                                 d_codes.ctypes.data, d_off.ctypes.data, n, out.ctypes.data)
     if rc != 0:
         raise ValueError(f"{symbol} refused its arguments ({rc})")
     return out
@@ -470,7 +487,7 @@ def align_pairs_flat(algo, q_codes, q_off, d_codes, d_off):
     return _align_flat("ssa_amd_align_pairs", "align_pairs_flat", algo, q_codes, q_off, d_codes, d_off)
 
 
-def _align_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off):
+def _align_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band=None):
     import numpy as np
     for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
         if a.dtype != t or not a.flags.c_contiguous:
@@ -484,8 +501,9 @@ def _align_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off):
     if n and q_off[n] >= q_off[0] and d_off[n] >= d_off[0]:
         cap = int(q_off[n] - q_off[0]) + int(d_off[n] - d_off[0]) + n
     cigars = np.zeros(cap, np.uint8)
-    rc = getattr(load(), symbol)(mode, q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data,
-                                 d_off.ctypes.data, n, out.ctypes.data, cigars.ctypes.data, cap)
+    band = _band_arrays(name, band, n)
+    rc = getattr(load(), symbol)(mode, *(b.ctypes.data for b in band), q_codes.ctypes.data, q_off.ctypes.data,
+                                 d_codes.ctypes.data, d_off.ctypes.data, n, out.ctypes.data, cigars.ctypes.data, cap)
     if rc != 0:
         raise ValueError(f"{symbol} refused its arguments ({rc})")
     return out, cigars
@@ -532,6 +550,51 @@ def align_pairs_ends(ends, queries, targets):
 def align_pairs_ends_flat(ends, q_codes, q_off, d_codes, d_off):
     """ssa_amd_align_pairs_ends on the C layout itself: (out, cigars) as align_pairs_flat."""
     return _align_flat("ssa_amd_align_pairs_ends", "align_pairs_ends_flat", ends, q_codes, q_off, d_codes, d_off)
+
+
+def default_band(qlens, dlens, w):
+    """The band of half-width w around both corners' diagonals, valid for
+    every mask: (lo, hi) int64 arrays with lo = min(0, n - m) - w and
+    hi = max(0, n - m) + w for m = qlens[i], n = dlens[i]."""
+    import numpy as np
+    diff = np.asarray(dlens, np.int64) - np.asarray(qlens, np.int64)
+    return np.minimum(0, diff) - int(w), np.maximum(0, diff) + int(w)
+
+
+def score_pairs_banded(ends, queries, targets, band_lo, band_hi):
+    """ssa_amd_score_pairs_banded: the ends-free score of queries[i] against
+    targets[i] under the mask `ends`, over the cells whose diagonal k =
+    (target position) - (query position) lies in [band_lo[i], band_hi[i]], as
+    an int64 array.  Raises ValueError when the library refuses the arguments
+    (a band that admits no alignment among them)."""
+    if len(queries) != len(targets):
+        raise ValueError("score_pairs_banded: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    return score_pairs_banded_flat(ends, q, qo, d, do, band_lo, band_hi)
+
+
+def score_pairs_banded_flat(ends, q_codes, q_off, d_codes, d_off, band_lo, band_hi):
+    """ssa_amd_score_pairs_banded on the C layout itself (score_pairs_flat's
+    arrays, and one int64 band_lo / band_hi entry per pair)."""
+    return _score_flat("ssa_amd_score_pairs_banded", "score_pairs_banded_flat", ends, q_codes, q_off, d_codes, d_off,
+                       band=(band_lo, band_hi))
+
+
+def align_pairs_banded(ends, queries, targets, band_lo, band_hi):
+    """ssa_amd_align_pairs_banded: [(score, (q_begin, q_end, d_begin, d_end),
+    cigar)] of the same alignments; shapes and errors as align_pairs_ends."""
+    if len(queries) != len(targets):
+        raise ValueError("align_pairs_banded: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    return _alignment_list(*align_pairs_banded_flat(ends, q, qo, d, do, band_lo, band_hi))
+
+
+def align_pairs_banded_flat(ends, q_codes, q_off, d_codes, d_off, band_lo, band_hi):
+    """ssa_amd_align_pairs_banded on the C layout itself: (out, cigars) as align_pairs_flat."""
+    return _align_flat("ssa_amd_align_pairs_banded", "align_pairs_banded_flat", ends, q_codes, q_off, d_codes, d_off,
+                       band=(band_lo, band_hi))
 
 
 def align_pairs_stats():

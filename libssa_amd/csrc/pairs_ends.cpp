@@ -22,23 +22,107 @@
 
 namespace ssa {
 
-namespace {
-
-// ------------------------------------------------------------ the host path
-struct EndCell {
-    int64_t score;
-    size_t q_end, d_end;
-};
-
+// --------------------------------- shared with pairs_banded.cpp (pairs_ends.h)
 // The rule among equal candidates: the greatest (d_end, q_end).  The kept
 // last-column cell (col_best at row col_row of column dn - 1) has the greatest
 // column there is, so the kept last-row cell (row_best at column row_col of row
 // qn - 1) wins a tie only as the corner.
-EndCell pick_end(int64_t row_best, size_t row_col, int64_t col_best, size_t col_row, size_t qn, size_t dn) {
+EndCell ends_pick_cell(int64_t row_best, size_t row_col, int64_t col_best, size_t col_row, size_t qn, size_t dn) {
     if (row_best > col_best || (row_best == col_best && row_col == dn - 1)) return EndCell{row_best, qn - 1, row_col};
     return EndCell{col_best, col_row, dn - 1};
 }
 
+// An empty side: 0 when both are empty or the other side has a free end or begin, else one gap over it.
+int64_t ends_empty_score(int ends, size_t qn, size_t dn, int64_t Q, int64_t R) {
+    if (qn + dn == 0) return 0;
+    const int free_bits = qn == 0 ? (kFreeDBegin | kFreeDEnd) : (kFreeQBegin | kFreeQEnd);
+    return (ends & free_bits) ? 0 : Q + (int64_t)(qn + dn) * R;
+}
+
+// The region and the text from the end cell and the walk's runs.  The walk
+// stands at (i, j) = end cell minus what the runs consumed.  Left through
+// column -1 at row i >= 0: a free q begin starts the region at row i + 1,
+// else the i + 1 rows above are a leading D run (the boundary's own gap, Q +
+// (i + 1) R); the same through row -1 with the d begin and I.  So the CIGAR
+// always spans the region and re-scores to the score.
+uint32_t ends_finish_alignment(int ends, size_t q_end, size_t d_end, std::vector<uint32_t>& runs, uint64_t region[4],
+                               char* text) {
+    int64_t qc = 0, dc = 0;
+    for (const uint32_t r : runs) {
+        if ((r & 3) != kOpI) qc += r >> 2;
+        if ((r & 3) != kOpD) dc += r >> 2;
+    }
+    const int64_t i = (int64_t)q_end - qc, j = (int64_t)d_end - dc;
+    uint64_t q_begin = 0, d_begin = 0;
+    auto lead = [&](uint32_t op, int64_t n) {
+        if (!runs.empty() && (runs.back() & 3) == op) runs.back() += (uint32_t)n << 2;
+        else runs.push_back((uint32_t)n << 2 | op);
+    };
+    if (j < 0 && i >= 0) {
+        if (ends & kFreeQBegin) q_begin = (uint64_t)i + 1;
+        else lead(kOpD, i + 1);
+    } else if (i < 0 && j >= 0) {
+        if (ends & kFreeDBegin) d_begin = (uint64_t)j + 1;
+        else lead(kOpI, j + 1);
+    }
+    region[0] = q_begin;
+    region[1] = q_end;
+    region[2] = d_begin;
+    region[3] = d_end;
+    return format_runs(runs.data(), (uint32_t)runs.size(), text);
+}
+
+// ---------------------------------------------------------------- arguments
+// ssa_amd_score_pairs' checks, and the mask's
+bool ends_args_ok(int ends, const uint8_t* qc, const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff,
+                  size_t n) {
+    if (ends < 0 || ends > 15) return false;
+    if (n == 0) return true;
+    if (!qc || !qoff || !dc || !doff) return false;
+    for (size_t i = 0; i < n; i++)
+        if (qoff[i + 1] < qoff[i] || doff[i + 1] < doff[i]) return false;
+    // every residue is a code < 32 (the matrix is 32 x 32)
+    std::atomic<uint32_t> seen{0};
+    auto scan = [&](const uint8_t* p, size_t len) {
+        parallel_ranges(len, 1 << 20, [&](size_t b, size_t e) {
+            uint8_t acc = 0;
+            for (size_t i = b; i < e; i++) acc |= p[i];
+            seen.fetch_or(acc);
+        });
+    };
+    scan(qc + qoff[0], qoff[n] - qoff[0]);
+    scan(dc + doff[0], doff[n] - doff[0]);
+    return seen.load() < (uint32_t)kDim;
+}
+
+// What the int32 kernels take (pairs.cpp, pairs_align.cpp): an int8 matrix,
+// gap penalties <= 0, and per pair at most residue_limit residues.  The bound
+// behind the limit, |H|, |E|, |F| <= (qlen + dlen) * (max |M| + |gap_extend|)
+// + 2 * |gap_open|, holds unchanged here: a free begin replaces a boundary
+// value Q + k R by 0, which is inside it, and an end maximum creates no new
+// value.  No symmetric-matrix condition (as for NW: every pass scores M[d][q]).
+void ends_route(EndsRouting& T, size_t n) {
+    const Config& C = cfg();
+    const int64_t* M = matrix().m;
+    const int64_t Q = C.gap_open, Ge = C.gap_extend;
+    int64_t max_abs = 0;
+    bool int8_matrix = true;
+    for (int i = 0; i < kDim * kDim; i++) {
+        if (M[i] < -128 || M[i] > 127) int8_matrix = false;
+        max_abs = std::max<int64_t>(max_abs, std::llabs(M[i]));
+    }
+    T.device = !C.pairs_host && int8_matrix && Q <= 0 && Ge <= 0 && n <= UINT32_MAX;
+    if (T.device) T.device = pairs_use_device(&T.dev_id, &T.stream);
+    const int64_t per_residue = max_abs + std::llabs(Ge);
+    T.residue_limit = per_residue ? (((int64_t)1 << 29) - 2 * std::llabs(Q)) / per_residue : INT64_MAX;
+    if (T.device)
+        for (int q = 0; q < kDim; q++)
+            for (int d = 0; d < kDim; d++) T.mt[q * 32 + d] = (int8_t)M[(d << 5) + q];
+}
+
+namespace {
+
+// ------------------------------------------------------------ the host path
 // One pair, both sides non-empty: score and end cell by the definition, in
 // int64; he = 2 * qn scratch words.  dir (or nullptr): qn * dn bytes, cell
 // (i, j) at dir[j * qn + i], the four kDir* bits -- directions()'s rule
@@ -84,14 +168,7 @@ EndCell host_ends(int ends, const uint8_t* d, size_t dn, const uint8_t* q, size_
                 col_best = he[2 * i];
                 col_row = i;
             }
-    return pick_end(row_best, row_col, col_best, col_row, qn, dn);
-}
-
-// An empty side: 0 when both are empty or the other side has a free end or begin, else one gap over it.
-int64_t empty_side_score(int ends, size_t qn, size_t dn, int64_t Q, int64_t R) {
-    if (qn + dn == 0) return 0;
-    const int free_bits = qn == 0 ? (kFreeDBegin | kFreeDEnd) : (kFreeQBegin | kFreeQEnd);
-    return (ends & free_bits) ? 0 : Q + (int64_t)(qn + dn) * R;
+    return ends_pick_cell(row_best, row_col, col_best, col_row, qn, dn);
 }
 
 // The walk (next_op, pairs_ends.h) from the end cell until it leaves the matrix: runs (count << 2 | op)
@@ -109,39 +186,6 @@ void host_walk(const uint8_t* dir, size_t qn, const EndCell& c, std::vector<uint
     }
 }
 
-// The region and the text from the end cell and the walk's runs.  The walk
-// stands at (i, j) = end cell minus what the runs consumed.  Left through
-// column -1 at row i >= 0: a free q begin starts the region at row i + 1,
-// else the i + 1 rows above are a leading D run (the boundary's own gap, Q +
-// (i + 1) R); the same through row -1 with the d begin and I.  So the CIGAR
-// always spans the region and re-scores to the score.
-uint32_t finish_alignment(int ends, size_t q_end, size_t d_end, std::vector<uint32_t>& runs, uint64_t region[4],
-                          char* text) {
-    int64_t qc = 0, dc = 0;
-    for (const uint32_t r : runs) {
-        if ((r & 3) != kOpI) qc += r >> 2;
-        if ((r & 3) != kOpD) dc += r >> 2;
-    }
-    const int64_t i = (int64_t)q_end - qc, j = (int64_t)d_end - dc;
-    uint64_t q_begin = 0, d_begin = 0;
-    auto lead = [&](uint32_t op, int64_t n) {
-        if (!runs.empty() && (runs.back() & 3) == op) runs.back() += (uint32_t)n << 2;
-        else runs.push_back((uint32_t)n << 2 | op);
-    };
-    if (j < 0 && i >= 0) {
-        if (ends & kFreeQBegin) q_begin = (uint64_t)i + 1;
-        else lead(kOpD, i + 1);
-    } else if (i < 0 && j >= 0) {
-        if (ends & kFreeDBegin) d_begin = (uint64_t)j + 1;
-        else lead(kOpI, j + 1);
-    }
-    region[0] = q_begin;
-    region[1] = q_end;
-    region[2] = d_begin;
-    region[3] = d_end;
-    return format_runs(runs.data(), (uint32_t)runs.size(), text);
-}
-
 // Per-thread scratch of the host path.
 struct HostScratch {
     std::vector<int64_t> he;
@@ -151,7 +195,7 @@ struct HostScratch {
 
 int64_t host_score(int ends, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, HostScratch& W) {
     const int64_t Q = cfg().gap_open, Ge = cfg().gap_extend;
-    if (ql == 0 || dl == 0) return empty_side_score(ends, ql, dl, Q, Ge);
+    if (ql == 0 || dl == 0) return ends_empty_score(ends, ql, dl, Q, Ge);
     if (W.he.size() < 2 * ql) W.he.resize(2 * ql);
     return host_ends(ends, d, dl, q, ql, matrix().m, Q, Ge, W.he.data(), nullptr).score;
 }
@@ -161,7 +205,7 @@ void host_align(int ends, const uint8_t* q, size_t ql, const uint8_t* d, size_t 
     const int64_t Q = cfg().gap_open, Ge = cfg().gap_extend;
     o.flags = 1;
     if (ql == 0 || dl == 0) {
-        o.score = empty_side_score(ends, ql, dl, Q, Ge);
+        o.score = ends_empty_score(ends, ql, dl, Q, Ge);
         for (auto& r : o.region) r = 0;
         o.cigar_len = 0;
         text[0] = 0;
@@ -172,62 +216,7 @@ void host_align(int ends, const uint8_t* q, size_t ql, const uint8_t* d, size_t 
     const EndCell c = host_ends(ends, d, dl, q, ql, matrix().m, Q, Ge, W.he.data(), W.dir.data());
     host_walk(W.dir.data(), ql, c, W.runs);
     o.score = c.score;
-    o.cigar_len = finish_alignment(ends, c.q_end, c.d_end, W.runs, o.region, text);
-}
-
-// ---------------------------------------------------------------- arguments
-// ssa_amd_score_pairs' checks, and the mask's
-bool args_ok(int ends, const uint8_t* qc, const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff, size_t n) {
-    if (ends < 0 || ends > 15) return false;
-    if (n == 0) return true;
-    if (!qc || !qoff || !dc || !doff) return false;
-    for (size_t i = 0; i < n; i++)
-        if (qoff[i + 1] < qoff[i] || doff[i + 1] < doff[i]) return false;
-    // every residue is a code < 32 (the matrix is 32 x 32)
-    std::atomic<uint32_t> seen{0};
-    auto scan = [&](const uint8_t* p, size_t len) {
-        parallel_ranges(len, 1 << 20, [&](size_t b, size_t e) {
-            uint8_t acc = 0;
-            for (size_t i = b; i < e; i++) acc |= p[i];
-            seen.fetch_or(acc);
-        });
-    };
-    scan(qc + qoff[0], qoff[n] - qoff[0]);
-    scan(dc + doff[0], doff[n] - doff[0]);
-    return seen.load() < (uint32_t)kDim;
-}
-
-// What the int32 kernels take (pairs.cpp, pairs_align.cpp): an int8 matrix,
-// gap penalties <= 0, and per pair at most residue_limit residues.  The bound
-// behind the limit, |H|, |E|, |F| <= (qlen + dlen) * (max |M| + |gap_extend|)
-// + 2 * |gap_open|, holds unchanged here: a free begin replaces a boundary
-// value Q + k R by 0, which is inside it, and an end maximum creates no new
-// value.  No symmetric-matrix condition (as for NW: every pass scores M[d][q]).
-struct Routing {
-    bool device = false;
-    int dev_id = -1;
-    hipStream_t stream = nullptr;
-    int64_t residue_limit = 0;
-    int8_t mt[kPairsCodes * 32] = {};   // the compact matrix, transposed: mt[q][d] = M[d][q], padding row zero
-};
-
-void route(Routing& T, size_t n) {
-    const Config& C = cfg();
-    const int64_t* M = matrix().m;
-    const int64_t Q = C.gap_open, Ge = C.gap_extend;
-    int64_t max_abs = 0;
-    bool int8_matrix = true;
-    for (int i = 0; i < kDim * kDim; i++) {
-        if (M[i] < -128 || M[i] > 127) int8_matrix = false;
-        max_abs = std::max<int64_t>(max_abs, std::llabs(M[i]));
-    }
-    T.device = !C.pairs_host && int8_matrix && Q <= 0 && Ge <= 0 && n <= UINT32_MAX;
-    if (T.device) T.device = pairs_use_device(&T.dev_id, &T.stream);
-    const int64_t per_residue = max_abs + std::llabs(Ge);
-    T.residue_limit = per_residue ? (((int64_t)1 << 29) - 2 * std::llabs(Q)) / per_residue : INT64_MAX;
-    if (T.device)
-        for (int q = 0; q < kDim; q++)
-            for (int d = 0; d < kDim; d++) T.mt[q * 32 + d] = (int8_t)M[(d << 5) + q];
+    o.cigar_len = ends_finish_alignment(ends, c.q_end, c.d_end, W.runs, o.region, text);
 }
 
 // ------------------------------------------------------------- device state
@@ -320,7 +309,7 @@ struct Chunk {
 // Cuts the chunk that starts at g0 (within the byte budget, at least one
 // group), packs it lane-interleaved into the pinned block and enqueues its
 // upload; sizes every device buffer the kernels of the chunk touch.
-Chunk pack_chunk(Batch& B, size_t g0, bool align, int ends, const Routing& T) {
+Chunk pack_chunk(Batch& B, size_t g0, bool align, int ends, const EndsRouting& T) {
     EndsDevice& P = g_dev;
     const Config& C = cfg();
     const size_t ngroups = B.groups.size(), npd = B.idx.size();
@@ -432,7 +421,7 @@ double elapsed(int e) {
 int score_pairs_ends(int ends, const uint8_t* qc, const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff,
                      size_t n, int64_t* scores) {
     const double t0 = now_ms();
-    if (!args_ok(ends, qc, qoff, dc, doff, n) || (n && !scores)) return 1;
+    if (!ends_args_ok(ends, qc, qoff, dc, doff, n) || (n && !scores)) return 1;
     ssa_amd_pairs_stats_t S{};
     S.strip_rows = kPairsRows;
     S.device = -1;
@@ -441,8 +430,8 @@ int score_pairs_ends(int ends, const uint8_t* qc, const uint64_t* qoff, const ui
         return 0;
     }
     if (!matrix().ready) fatal("Scoring matrix not initialized");
-    Routing T;
-    route(T, n);
+    EndsRouting T;
+    ends_route(T, n);
     S.pairs = n;
     S.device = T.device ? T.dev_id : -1;
     snprintf(S.kernel, sizeof S.kernel, "pairs_ends_i32");
@@ -503,7 +492,7 @@ int score_pairs_ends(int ends, const uint8_t* qc, const uint64_t* qoff, const ui
 int align_pairs_ends(int ends, const uint8_t* qc, const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff,
                      size_t n, ssa_amd_pair_alignment_t* out, char* cigars, size_t cigar_cap) {
     const double t0 = now_ms();
-    if (!args_ok(ends, qc, qoff, dc, doff, n) || (n && (!out || !cigars))) return 1;
+    if (!ends_args_ok(ends, qc, qoff, dc, doff, n) || (n && (!out || !cigars))) return 1;
     ssa_amd_align_pairs_stats_t S{};
     S.device = -1;
     if (n == 0) {
@@ -517,8 +506,8 @@ int align_pairs_ends(int ends, const uint8_t* qc, const uint64_t* qoff, const ui
     for (size_t i = 0; i < n; i++) coff[i + 1] = coff[i] + (qoff[i + 1] - qoff[i]) + (doff[i + 1] - doff[i]) + 1;
     if (cigar_cap < coff[n]) return 1;
 
-    Routing T;
-    route(T, n);
+    EndsRouting T;
+    ends_route(T, n);
     S.pairs = n;
     S.device = T.device ? T.dev_id : -1;
 
@@ -597,7 +586,8 @@ int align_pairs_ends(int ends, const uint8_t* qc, const uint64_t* qoff, const ui
                     const uint32_t pos = (uint32_t)h_out[l].y;
                     const uint32_t nr = std::min(h_nruns[l], L.cap);
                     runs.assign(h_runs + L.slot, h_runs + L.slot + nr);
-                    o.cigar_len = finish_alignment(ends, pos & 0xffff, pos >> 16, runs, o.region, cigars + coff[i]);
+                    o.cigar_len =
+                        ends_finish_alignment(ends, pos & 0xffff, pos >> 16, runs, o.region, cigars + coff[i]);
                 }
             });
             S.text_ms += now_ms() - tt0;

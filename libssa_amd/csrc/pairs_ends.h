@@ -47,4 +47,30 @@ struct EndsArgs {
 // pass: 0 scores (ends_kernel<false>), 1 scores and directions (ends_kernel<true>), 2 the walk
 hipError_t launch_pairs_ends(int pass, const EndsArgs& a, hipStream_t st);
 
+// ------------------------------------------- shared with pairs_banded.cpp
+// (host side, defined in pairs_ends.cpp)
+struct EndCell {
+    int64_t score;
+    size_t q_end, d_end;
+};
+// the tie rule between the kept last-row and last-column candidates
+EndCell ends_pick_cell(int64_t row_best, size_t row_col, int64_t col_best, size_t col_row, size_t qn, size_t dn);
+// the closed form of a pair with an empty side
+int64_t ends_empty_score(int ends, size_t qn, size_t dn, int64_t Q, int64_t R);
+// region and text from the end cell and the walk's runs (leading run where a begin is not free)
+uint32_t ends_finish_alignment(int ends, size_t q_end, size_t d_end, std::vector<uint32_t>& runs, uint64_t region[4],
+                               char* text);
+// ssa_amd_score_pairs' argument checks, and the mask's
+bool ends_args_ok(int ends, const uint8_t* qc, const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff,
+                  size_t n);
+// what the int32 kernels take: device or not, the residue limit behind the 2^29 bound, the compact matrix
+struct EndsRouting {
+    bool device = false;
+    int dev_id = -1;
+    hipStream_t stream = nullptr;
+    int64_t residue_limit = 0;
+    int8_t mt[kPairsCodes * 32] = {};   // the compact matrix, transposed: mt[q][d] = M[d][q], padding row zero
+};
+void ends_route(EndsRouting& T, size_t n);
+
 }  // namespace ssa
