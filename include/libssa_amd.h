@@ -544,6 +544,73 @@ int ssa_amd_align_pairs_banded( int ends, const int64_t * band_lo, const int64_t
                                 const uint8_t * d_codes, const uint64_t * d_off, size_t npairs,
                                 ssa_amd_pair_alignment_t * out, char * cigars, size_t cigar_cap );
 
+/* Local begin / end modes of the banded calls: Smith-Waterman inside a band,
+ * and extension alignment.  `mode` is a mask of the four SSA_AMD_FREE_* bits
+ * and of: */
+#define SSA_AMD_LOCAL_BEGIN 16  /* the alignment may begin at any cell */
+#define SSA_AMD_LOCAL_END   32  /* ... and end at any cell */
+/* Modes 0..63 are legal.  The CANONICAL mode adds FREE_Q_BEGIN | FREE_D_BEGIN
+ * when LOCAL_BEGIN is set and FREE_Q_END | FREE_D_END when LOCAL_END is set;
+ * every mode behaves exactly as its canonical one.  The 25 canonical modes:
+ * 0..15; 21, 23, 29, 31 (local begin; end = corner / q free / d free / both
+ * free); 42, 43, 46, 47 (local end; begin = fixed / q free / d free / both
+ * free); 63.  Mode 63 is Smith-Waterman, 42 extends to the right from a fixed
+ * begin, 21 to the left towards a fixed end.
+ * Everything not said here is the banded definition above: rows = q, columns =
+ * d, scores M[d][q], gaps gap_open + L * gap_extend, a cell exists iff its
+ * diagonal k = j - i is in [lo, hi], minus infinity outside the band, a
+ * boundary cell whose begin is not free needs diagonal 0 in the band.
+ * LOCAL_BEGIN: every existing boundary cell is 0; every existing real cell has
+ * H(i, j) = max(0, D, E, F) with D = H(i-1, j-1) + M[d_j][q_i], and STOP(i, j)
+ * holds iff max(D, E, F) <= 0 (the floor wins ties: the shortest alignment);
+ * E and F are computed from the floored H; a cell outside the band is minus
+ * infinity, not 0.
+ * LOCAL_END: the end candidates are all existing real cells with a finite H;
+ * the score is max(0, greatest candidate H); if that is 0 the result is the
+ * empty alignment, else the end cell is the candidate with the greatest H and
+ * among equal ones the SMALLEST (d_end, q_end) in lexicographic order (the
+ * cell the reference's forward SW pass picks).  Without LOCAL_END candidates
+ * and the greatest-(d_end, q_end) rule are the ends-free calls'.
+ * The walk is ssa_amd_align_pairs_ends' with one addition: at a cell it stands
+ * on through its H -- the end cell, a cell reached by M, or one reached by a
+ * gap whose extension bit is not set -- it first tests STOP and, if set, stops
+ * there; that cell is not part of the alignment (q begin = i + 1, d begin =
+ * j + 1).  Leaving through row -1 or column -1 works as before under the
+ * canonical mode.  The score is the end cell's H; the region is inclusive; the
+ * CIGAR re-scored from (q begin, d begin) gives exactly the score and ends at
+ * (q end + 1, d end + 1); every visited cell lies in the band.  With a local
+ * bit set, score 0 <=> empty CIGAR <=> region (0, 0, 0, 0), counted in
+ * zero_pairs.
+ * A band is VALID iff lo <= hi and [lo, hi] meets the start diagonals
+ * [FREE_Q_BEGIN ? -qlen : 0, FREE_D_BEGIN ? dlen : 0] and the end diagonals of
+ * the canonical mode (under LOCAL_END every real cell's diagonal,
+ * [-(qlen - 1), dlen - 1]); a band that holds no real cell of the pair is
+ * refused, under mode 63 too.  An invalid band of a pair with two non-empty
+ * sides makes the call return non-zero before anything runs.  An empty side
+ * ignores its band: score 0 with either local bit, region zeros, empty CIGAR.
+ * Band values are clamped as above.  band_lo == band_hi == NULL means
+ * unbanded (lo = -qlen - 1, hi = dlen + 1 for every pair); exactly one of them
+ * NULL is refused, as is a mode outside 0..63.
+ * Arguments, checks, return codes, the CIGAR buffer bound, options
+ * ("pairs_chunk", "pairs_host"), device choice and statistics getters are the
+ * banded calls'.  A canonical mode below 16 is handed to
+ * ssa_amd_*_pairs_banded (with bands) or ssa_amd_*_pairs_ends (NULL bands)
+ * unchanged: results and statistics are those calls'.  With a local bit the
+ * score call reports kernel "pairs_local_i32"; the align call reports kernels
+ * "pairs_local_end,pairs_local_dir,pairs_local_walk" under LOCAL_END (fwd_ms =
+ * the end-cell pass) and "pairs_local_dir,pairs_local_walk" under LOCAL_BEGIN
+ * alone (fwd_ms = 0); rev_ms = 0, kernel_ms is the sum, dir_bytes counts the
+ * direction bits and the STOP bits.  Device conditions are the banded calls'
+ * (no symmetric matrix needed; the 512 MiB of a pair include its STOP bits). */
+int ssa_amd_score_pairs_local( int mode, const int64_t * band_lo, const int64_t * band_hi,
+                               const uint8_t * q_codes, const uint64_t * q_off,
+                               const uint8_t * d_codes, const uint64_t * d_off,
+                               size_t npairs, int64_t * scores );
+int ssa_amd_align_pairs_local( int mode, const int64_t * band_lo, const int64_t * band_hi,
+                               const uint8_t * q_codes, const uint64_t * q_off,
+                               const uint8_t * d_codes, const uint64_t * d_off, size_t npairs,
+                               ssa_amd_pair_alignment_t * out, char * cigars, size_t cigar_cap );
+
 #ifdef __cplusplus
 }
 #endif

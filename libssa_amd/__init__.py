@@ -116,7 +116,8 @@ EXPORTS = {
                       "ssa_amd_get_devices", "ssa_amd_score_pairs", "ssa_amd_get_pairs_stats",
                       "ssa_amd_map_residues", "ssa_amd_align_pairs", "ssa_amd_get_align_pairs_stats",
                       "ssa_amd_score_pairs_ends", "ssa_amd_align_pairs_ends",
-                      "ssa_amd_score_pairs_banded", "ssa_amd_align_pairs_banded"],
+                      "ssa_amd_score_pairs_banded", "ssa_amd_align_pairs_banded",
+                      "ssa_amd_score_pairs_local", "ssa_amd_align_pairs_local"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -178,6 +179,10 @@ def load():
                                         c_void_p], c_int),
         "ssa_amd_align_pairs_banded": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                         c_void_p, c_void_p, c_size_t], c_int),
+        "ssa_amd_score_pairs_local": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p], c_int),
+        "ssa_amd_align_pairs_local": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p, c_void_p, c_size_t], c_int),
         "ssa_amd_map_residues": ([c_char_p, c_size_t, c_char_p, c_size_t], c_size_t),
         "ssa_amd_shard_bounds": ([c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_size_t)], c_int),
     }
@@ -426,10 +431,15 @@ def score_pairs_flat(algo, q_codes, q_off, d_codes, d_off):
 
 
 def _band_arrays(name, band, n):
-    """(band_lo, band_hi) as contiguous int64 arrays of n entries, or None for an unbanded call."""
+    """(band_lo, band_hi) as contiguous int64 arrays of n entries; () for a
+    call without band arguments; a (None, None) band stays two NULL pointers."""
     import numpy as np
     if band is None:
         return ()
+    if band[0] is None and band[1] is None:
+        return None, None
+    if band[0] is None or band[1] is None:
+        raise ValueError(f"{name}: band_lo and band_hi are given together or not at all")
     lo, hi = (np.ascontiguousarray(b, np.int64) for b in band)
     if lo.shape != (n,) or hi.shape != (n,):
         raise ValueError(f"{name}: band_lo and band_hi of npairs entries expected")
@@ -446,7 +456,7 @@ def _score_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band=None):
     n = len(q_off) - 1
     out = np.zeros(n, np.int64)
     band = _band_arrays(name, band, n)
-    rc = getattr(load(), symbol)(mode, *(b.ctypes.data for b in band), q_codes.ctypes.data, q_off.ctypes.data,
+    rc = getattr(load(), symbol)(mode, *(None if b is None else b.ctypes.data for b in band), q_codes.ctypes.data, q_off.ctypes.data,
                                  d_codes.ctypes.data, d_off.ctypes.data, n, out.ctypes.data)
     if rc != 0:
         raise ValueError(f"{symbol} refused its arguments ({rc})")
@@ -502,7 +512,7 @@ def _align_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band=None):
         cap = int(q_off[n] - q_off[0]) + int(d_off[n] - d_off[0]) + n
     cigars = np.zeros(cap, np.uint8)
     band = _band_arrays(name, band, n)
-    rc = getattr(load(), symbol)(mode, *(b.ctypes.data for b in band), q_codes.ctypes.data, q_off.ctypes.data,
+    rc = getattr(load(), symbol)(mode, *(None if b is None else b.ctypes.data for b in band), q_codes.ctypes.data, q_off.ctypes.data,
                                  d_codes.ctypes.data, d_off.ctypes.data, n, out.ctypes.data, cigars.ctypes.data, cap)
     if rc != 0:
         raise ValueError(f"{symbol} refused its arguments ({rc})")
@@ -594,6 +604,45 @@ def align_pairs_banded(ends, queries, targets, band_lo, band_hi):
 def align_pairs_banded_flat(ends, q_codes, q_off, d_codes, d_off, band_lo, band_hi):
     """ssa_amd_align_pairs_banded on the C layout itself: (out, cigars) as align_pairs_flat."""
     return _align_flat("ssa_amd_align_pairs_banded", "align_pairs_banded_flat", ends, q_codes, q_off, d_codes, d_off,
+                       band=(band_lo, band_hi))
+
+
+# local begin / end: the mode bits of ssa_amd_*_pairs_local beside the FREE_* ones
+LOCAL_BEGIN, LOCAL_END, LOCAL = 16, 32, 48
+
+
+def score_pairs_local(mode, queries, targets, band_lo=None, band_hi=None):
+    """ssa_amd_score_pairs_local: the score of queries[i] against targets[i]
+    under `mode` (FREE_* and LOCAL_* bits; LOCAL = 48 is Smith-Waterman) inside
+    the bands, as an int64 array; band_lo = band_hi = None is unbanded (NULL
+    pointers).  Raises ValueError when the library refuses the arguments."""
+    if len(queries) != len(targets):
+        raise ValueError("score_pairs_local: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    return score_pairs_local_flat(mode, q, qo, d, do, band_lo, band_hi)
+
+
+def score_pairs_local_flat(mode, q_codes, q_off, d_codes, d_off, band_lo=None, band_hi=None):
+    """ssa_amd_score_pairs_local on the C layout itself (score_pairs_banded_flat's arrays)."""
+    return _score_flat("ssa_amd_score_pairs_local", "score_pairs_local_flat", mode, q_codes, q_off, d_codes, d_off,
+                       band=(band_lo, band_hi))
+
+
+def align_pairs_local(mode, queries, targets, band_lo=None, band_hi=None):
+    """ssa_amd_align_pairs_local: [(score, (q_begin, q_end, d_begin, d_end),
+    cigar)] of the same alignments; a zero score has region zeros and an
+    empty CIGAR.  Shapes and errors as align_pairs_banded."""
+    if len(queries) != len(targets):
+        raise ValueError("align_pairs_local: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    return _alignment_list(*align_pairs_local_flat(mode, q, qo, d, do, band_lo, band_hi))
+
+
+def align_pairs_local_flat(mode, q_codes, q_off, d_codes, d_off, band_lo=None, band_hi=None):
+    """ssa_amd_align_pairs_local on the C layout itself: (out, cigars) as align_pairs_flat."""
+    return _align_flat("ssa_amd_align_pairs_local", "align_pairs_local_flat", mode, q_codes, q_off, d_codes, d_off,
                        band=(band_lo, band_hi))
 
 

@@ -214,6 +214,13 @@ int score_pairs_banded(int ends, const int64_t* band_lo, const int64_t* band_hi,
 int align_pairs_banded(int ends, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* q_codes,
                        const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off, size_t npairs,
                        ssa_amd_pair_alignment_t* out, char* cigars, size_t cigar_cap);
+// pairs_local.cpp: ssa_amd_score_pairs_local / ssa_amd_align_pairs_local; the same two statistics
+int score_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* q_codes,
+                      const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off, size_t npairs,
+                      int64_t* scores);
+int align_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* q_codes,
+                      const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off, size_t npairs,
+                      ssa_amd_pair_alignment_t* out, char* cigars, size_t cigar_cap);
 void set_pairs_stats(const ssa_amd_pairs_stats_t& s);
 void set_align_pairs_stats(const ssa_amd_align_pairs_stats_t& s);
 

@@ -11,19 +11,18 @@
 // banded_kernel<false>, a chunk of the align call banded_kernel<true> and
 // banded_walk_kernel back to back.  What the device does not take goes
 // through the int64 routine below, which keeps H, F and its direction bytes
-// for the band only (rows x band width), in parallel on the host.
+// for the band only (rows x band width), in parallel on the host.  The band's
+// rule, the ordered batch, the chunk packer and the device buffers are declared
+// in pairs_banded_host.h: the local pair calls (pairs_local.cpp) use them too.
 #include <algorithm>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
-#include "pairs_banded.h"
-#include "pairs_host.h"
+#include "pairs_banded_host.h"
 
 namespace ssa {
-
-namespace {
 
 // ------------------------------------------------------------------ the band
 // Diagonals of a pair's cells, boundaries included, lie in [-qlen, dlen]; values
@@ -41,6 +40,8 @@ bool band_valid(int ends, int64_t m, int64_t n, int64_t lo, int64_t hi) {
     const int64_t e_lo = (ends & kFreeDEnd) ? -(m - 1) : n - m, e_hi = (ends & kFreeQEnd) ? n - 1 : n - m;
     return lo <= s_hi && hi >= s_lo && lo <= e_hi && hi >= e_lo;
 }
+
+namespace {
 
 // ------------------------------------------------------------ the host path
 constexpr int64_t kNeg = INT64_MIN / 4;     // minus infinity: room for every sum that starts from it
@@ -193,21 +194,16 @@ bool bands_ok(int ends, const int64_t* band_lo, const int64_t* band_hi, const ui
 }
 
 // ------------------------------------------------------------- device state
-constexpr size_t kScoreChunkBudget = (size_t)256 << 20;   // ssa_amd_score_pairs'
-constexpr size_t kAlignChunkBudget = (size_t)2 << 30;     // ssa_amd_align_pairs_ends'
-constexpr size_t kPairDirBudget = (size_t)512 << 20;      // direction bits of one pair alone
+BandedDevice g_dev;
 
-struct BandedDevice {
-    int device = -1;
-    hipEvent_t ev[3] = {};
-    bool events = false;
-    PairsBuf up, bnd, dir, runs, out;
-} g_dev;
+}  // namespace
 
-void prepare_device(int dev_id) {
+BandedDevice& banded_device() { return g_dev; }
+
+void banded_prepare_device(int dev_id) {
     BandedDevice& P = g_dev;
     if (P.device != dev_id) {
-        for (PairsBuf* b : {&P.up, &P.bnd, &P.dir, &P.runs, &P.out}) b->release();
+        for (PairsBuf* b : {&P.up, &P.bnd, &P.dir, &P.runs, &P.out, &P.stop}) b->release();
         P.device = dev_id;
     }
     if (!P.events) {
@@ -223,115 +219,86 @@ uint64_t pair_dir_rows(uint64_t ql, uint64_t dl, int64_t lo, int64_t hi) {
     return (ql + 7) / 8 * blocks;
 }
 
-// The device pairs of a call, ordered by shape and band and cut into groups of 64.
-struct Batch {
-    const uint8_t* qc;
-    const uint64_t* qoff;
-    const uint8_t* dc;
-    const uint64_t* doff;
-    const int64_t* lo;                  // clamped, by input index
-    const int64_t* hi;
-    std::vector<uint32_t> idx;          // by input index
-    std::vector<BandGroup> groups;
-    std::vector<BandStrip> strips;      // all groups'; BandGroup::s_row is global until a chunk is cut
-    std::vector<uint64_t> drows;        // direction rows of each group
-    std::vector<size_t> gbytes;         // device bytes of each group
-
-    uint32_t qlen(size_t i) const { return (uint32_t)(qoff[i + 1] - qoff[i]); }
-    uint32_t dlen(size_t i) const { return (uint32_t)(doff[i + 1] - doff[i]); }
-    uint32_t nstrips(size_t i) const { return (qlen(i) + kPairsRows - 1) / kPairsRows; }
-
-    // A wave sweeps, strip by strip, the union of its lanes' in-band columns: order by strip count
-    // (longest first), then by the band's position, so that the union is little wider than one lane's.
-    // Returns the cells the waves walk.
-    uint64_t order(bool align) {
-        struct Key {
-            uint32_t strips;
-            int64_t lo, hi;
-            uint32_t pair;
-        };
-        std::vector<Key> keys(idx.size());
-        for (size_t p = 0; p < keys.size(); p++) keys[p] = Key{nstrips(idx[p]), lo[idx[p]], hi[idx[p]], idx[p]};
-        std::sort(keys.begin(), keys.end(), [](const Key& x, const Key& y) {
-            if (x.strips != y.strips) return x.strips > y.strips;
-            if (x.lo != y.lo) return x.lo < y.lo;
-            if (x.hi != y.hi) return x.hi < y.hi;
-            return x.pair < y.pair;
-        });
-        for (size_t p = 0; p < keys.size(); p++) idx[p] = keys[p].pair;
-        const size_t ngroups = (idx.size() + 63) / 64;
-        groups.assign(ngroups, BandGroup{});
-        drows.assign(ngroups, 0);
-        gbytes.assign(ngroups, 0);
-        strips.clear();
-        uint64_t swept = 0;
-        for (size_t g = 0; g < ngroups; g++) {
-            const size_t p0 = g * 64, p1 = std::min(idx.size(), g * 64 + 64);
-            uint32_t md = 0, ms = 0;
-            uint64_t ops = 0;
-            for (size_t p = p0; p < p1; p++) {
-                md = std::max(md, dlen(idx[p]));
-                ms = std::max(ms, nstrips(idx[p]));
-                ops += (uint64_t)qlen(idx[p]) + dlen(idx[p]);
-            }
-            BandGroup& G = groups[g];
-            G.ncb = (md + 3) / 4;
-            G.nstrips = ms;
-            G.s_row = (uint32_t)strips.size();
-            // the strips' ranges: the union over the lanes that have the strip of [8 s + lo, 8 s + 7 + hi] inside
-            // the lane's own columns (signed arithmetic: a range may be empty on either side)
-            uint64_t rows = 0;
-            for (uint32_t s = 0; s < ms; s++) {
-                int64_t a = INT64_MAX, b = -1;
-                for (size_t p = p0; p < p1; p++) {
-                    const uint32_t i = idx[p];
-                    if (nstrips(i) <= s) continue;
-                    const int64_t ca = std::max<int64_t>(0, (int64_t)s * kPairsRows + lo[i]);
-                    const int64_t cb = std::min<int64_t>((int64_t)dlen(i) - 1, (int64_t)s * kPairsRows + 7 + hi[i]);
-                    if (ca > cb) continue;
-                    a = std::min(a, ca);
-                    b = std::max(b, cb);
-                }
-                BandStrip S{};
-                if (a <= b) {
-                    S.cb0 = (uint32_t)(a / 4);
-                    S.ncb = (uint32_t)(b / 4) + 1 - S.cb0;
-                }
-                S.d_off = (uint32_t)rows;
-                rows += S.ncb;
-                strips.push_back(S);
-            }
-            drows[g] = rows;
-            swept += rows * 4 * kPairsRows * 64;
-            // residues, bnd, the strip table, per-lane words; the align call: direction bits and run slots
-            gbytes[g] = (size_t)G.ncb * 256 + (size_t)G.nstrips * 512 + (size_t)G.ncb * 4 * 512 +
-                        (size_t)ms * sizeof(BandStrip) +
-                        64 * (sizeof(uint2) + sizeof(int2) + sizeof(AlignLane) + sizeof(int2)) + sizeof(BandGroup);
-            if (align) gbytes[g] += (size_t)rows * 1024 + ops * 4;
+// A wave sweeps, strip by strip, the union of its lanes' in-band columns: order by strip count
+// (longest first), then by the band's position, so that the union is little wider than one lane's.
+uint64_t BandBatch::order(bool align, size_t row_bytes) {
+    struct Key {
+        uint32_t strips;
+        int64_t lo, hi;
+        uint32_t pair;
+    };
+    std::vector<Key> keys(idx.size());
+    for (size_t p = 0; p < keys.size(); p++) keys[p] = Key{nstrips(idx[p]), lo[idx[p]], hi[idx[p]], idx[p]};
+    std::sort(keys.begin(), keys.end(), [](const Key& x, const Key& y) {
+        if (x.strips != y.strips) return x.strips > y.strips;
+        if (x.lo != y.lo) return x.lo < y.lo;
+        if (x.hi != y.hi) return x.hi < y.hi;
+        return x.pair < y.pair;
+    });
+    for (size_t p = 0; p < keys.size(); p++) idx[p] = keys[p].pair;
+    const size_t ngroups = (idx.size() + 63) / 64;
+    groups.assign(ngroups, BandGroup{});
+    drows.assign(ngroups, 0);
+    gbytes.assign(ngroups, 0);
+    strips.clear();
+    uint64_t swept = 0;
+    for (size_t g = 0; g < ngroups; g++) {
+        const size_t p0 = g * 64, p1 = std::min(idx.size(), g * 64 + 64);
+        uint32_t md = 0, ms = 0;
+        uint64_t ops = 0;
+        for (size_t p = p0; p < p1; p++) {
+            md = std::max(md, dlen(idx[p]));
+            ms = std::max(ms, nstrips(idx[p]));
+            ops += (uint64_t)qlen(idx[p]) + dlen(idx[p]);
         }
-        return swept;
+        BandGroup& G = groups[g];
+        G.ncb = (md + 3) / 4;
+        G.nstrips = ms;
+        G.s_row = (uint32_t)strips.size();
+        // the strips' ranges: the union over the lanes that have the strip of [8 s + lo, 8 s + 7 + hi] inside
+        // the lane's own columns (signed arithmetic: a range may be empty on either side)
+        uint64_t rows = 0;
+        for (uint32_t s = 0; s < ms; s++) {
+            int64_t a = INT64_MAX, b = -1;
+            for (size_t p = p0; p < p1; p++) {
+                const uint32_t i = idx[p];
+                if (nstrips(i) <= s) continue;
+                const int64_t ca = std::max<int64_t>(0, (int64_t)s * kPairsRows + lo[i]);
+                const int64_t cb = std::min<int64_t>((int64_t)dlen(i) - 1, (int64_t)s * kPairsRows + 7 + hi[i]);
+                if (ca > cb) continue;
+                a = std::min(a, ca);
+                b = std::max(b, cb);
+            }
+            BandStrip S{};
+            if (a <= b) {
+                S.cb0 = (uint32_t)(a / 4);
+                S.ncb = (uint32_t)(b / 4) + 1 - S.cb0;
+            }
+            S.d_off = (uint32_t)rows;
+            rows += S.ncb;
+            strips.push_back(S);
+        }
+        drows[g] = rows;
+        swept += rows * 4 * kPairsRows * 64;
+        // residues, bnd, the strip table, per-lane words; the align call: direction bits and run slots
+        gbytes[g] = (size_t)G.ncb * 256 + (size_t)G.nstrips * 512 + (size_t)G.ncb * 4 * 512 +
+                    (size_t)ms * sizeof(BandStrip) +
+                    64 * (sizeof(uint2) + sizeof(int2) + sizeof(AlignLane) + sizeof(int2)) + sizeof(BandGroup);
+        if (align) gbytes[g] += (size_t)rows * row_bytes + ops * 4;
     }
-};
-
-// One chunk: groups [g0, g1) laid out in the upload block, packed and uploaded.
-struct Chunk {
-    size_t g0, g1, ng, nl, p0, p1;
-    uint64_t drow = 0;                  // the align call: 64-lane uint4 rows of direction bits
-    uint64_t nruns = 0;                 //   and run slots
-    AlignLane* lanes = nullptr;         //   the host copy of the lanes
-    BandedArgs A{};
-};
+    return swept;
+}
 
 // Cuts the chunk that starts at g0 (within the byte budget, at least one
 // group), packs it lane-interleaved into the pinned block and enqueues its
 // upload; sizes every device buffer the kernels of the chunk touch.
-Chunk pack_chunk(Batch& B, size_t g0, bool align, int ends, const EndsRouting& T) {
+BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const EndsRouting& T) {
     BandedDevice& P = g_dev;
     const Config& C = cfg();
     const size_t ngroups = B.groups.size(), npd = B.idx.size();
     const size_t chunk_groups = C.pairs_chunk > 0 ? std::max<size_t>(1, (size_t)C.pairs_chunk / 64) : SIZE_MAX;
-    const size_t budget = align ? kAlignChunkBudget : kScoreChunkBudget;
-    Chunk K;
+    const size_t budget = align ? kBandAlignChunkBudget : kBandScoreChunkBudget;
+    BandChunk K;
     size_t g1 = g0, bytes = 0;
     uint64_t trow = 0, qrow = 0, brow = 0, drow = 0, srow = 0;
     const uint32_t s_first = B.groups[g0].s_row;
@@ -442,13 +409,11 @@ Chunk pack_chunk(Batch& B, size_t g0, bool align, int ends, const EndsRouting& T
     return K;
 }
 
-double elapsed(int e) {
+double banded_elapsed(int e) {
     float ms = 0;
     check(hipEventElapsedTime(&ms, g_dev.ev[e], g_dev.ev[e + 1]), "hipEventElapsedTime");
     return (double)ms;
 }
-
-}  // namespace
 
 int score_pairs_banded(int ends, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* qc,
                        const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff, size_t n, int64_t* scores) {
@@ -470,7 +435,7 @@ int score_pairs_banded(int ends, const int64_t* band_lo, const int64_t* band_hi,
     S.device = T.device ? T.dev_id : -1;
     snprintf(S.kernel, sizeof S.kernel, "pairs_banded_i32");
 
-    Batch B{qc, qoff, dc, doff, lo.data(), hi.data(), {}, {}, {}, {}, {}};
+    BandBatch B{qc, qoff, dc, doff, lo.data(), hi.data(), {}, {}, {}, {}, {}};
     std::vector<size_t> todo;        // the pairs of the host path
     for (size_t i = 0; i < n; i++) {
         const uint64_t ql = qoff[i + 1] - qoff[i], dl = doff[i + 1] - doff[i];
@@ -496,14 +461,14 @@ int score_pairs_banded(int ends, const int64_t* band_lo, const int64_t* band_hi,
     // ---- the device path
     if (!B.idx.empty()) {
         BandedDevice& P = g_dev;
-        prepare_device(T.dev_id);
+        banded_prepare_device(T.dev_id);
         const double tp0 = now_ms();
         S.swept_cells = B.order(false);
         S.groups = (uint32_t)B.groups.size();
         S.pack_ms += now_ms() - tp0;
         for (size_t g0 = 0; g0 < B.groups.size();) {
             const double tc0 = now_ms();
-            const Chunk K = pack_chunk(B, g0, false, ends, T);
+            const BandChunk K = banded_pack_chunk(B, g0, false, ends, T);
             S.pack_ms += now_ms() - tc0;
             check(hipEventRecord(P.ev[0], T.stream), "hipEventRecord");
             check(launch_pairs_banded(0, K.A, T.stream), "pairs_banded_i32");
@@ -511,7 +476,7 @@ int score_pairs_banded(int ends, const int64_t* band_lo, const int64_t* band_hi,
             check(hipMemcpyAsync(P.out.h, P.out.d, K.nl * sizeof(int2), hipMemcpyDeviceToHost, T.stream),
                   "pairs_banded scores copy");
             check(hipStreamSynchronize(T.stream), "pairs_banded synchronize");
-            S.kernel_ms += elapsed(0);
+            S.kernel_ms += banded_elapsed(0);
             const int2* h_out = (const int2*)P.out.h;
             for (size_t p = K.p0; p < K.p1; p++) scores[B.idx[p]] = h_out[p - K.p0].x;
             S.chunks++;
@@ -549,14 +514,14 @@ int align_pairs_banded(int ends, const int64_t* band_lo, const int64_t* band_hi,
     S.pairs = n;
     S.device = T.device ? T.dev_id : -1;
 
-    Batch B{qc, qoff, dc, doff, lo.data(), hi.data(), {}, {}, {}, {}, {}};
+    BandBatch B{qc, qoff, dc, doff, lo.data(), hi.data(), {}, {}, {}, {}, {}};
     std::vector<size_t> todo;        // the pairs of the host path
     for (size_t i = 0; i < n; i++) {
         const uint64_t ql = qoff[i + 1] - qoff[i], dl = doff[i + 1] - doff[i];
         S.cells += ql * dl;
         // the ends call's conditions, with the direction bits of the band alone: at most 512 MiB for the pair
         if (T.device && ql && dl && (int64_t)(ql + dl) <= T.residue_limit && ql < kAlignMaxLen && dl < kAlignMaxLen &&
-            pair_dir_rows(ql, dl, lo[i], hi[i]) * 1024 <= kPairDirBudget)
+            pair_dir_rows(ql, dl, lo[i], hi[i]) * kBandDirRowBytes <= kBandPairDirBudget)
             B.idx.push_back((uint32_t)i);
         else
             todo.push_back(i);
@@ -578,7 +543,7 @@ int align_pairs_banded(int ends, const int64_t* band_lo, const int64_t* band_hi,
     // ---- the device path
     if (!B.idx.empty()) {
         BandedDevice& P = g_dev;
-        prepare_device(T.dev_id);
+        banded_prepare_device(T.dev_id);
         snprintf(S.kernels, sizeof S.kernels, "pairs_banded_dir,pairs_banded_walk");
         const double tp0 = now_ms();
         B.order(true);
@@ -586,7 +551,7 @@ int align_pairs_banded(int ends, const int64_t* band_lo, const int64_t* band_hi,
         S.pack_ms += now_ms() - tp0;
         for (size_t g0 = 0; g0 < B.groups.size();) {
             const double tc0 = now_ms();
-            const Chunk K = pack_chunk(B, g0, true, ends, T);
+            const BandChunk K = banded_pack_chunk(B, g0, true, ends, T);
             S.pack_ms += now_ms() - tc0;
             S.dir_bytes += K.drow * 1024;
             // ---- directions (with the score and the end cell), then the walk from that end cell
@@ -602,8 +567,8 @@ int align_pairs_banded(int ends, const int64_t* band_lo, const int64_t* band_hi,
                 check(hipMemcpyAsync(P.runs.h, P.runs.d, K.nruns * sizeof(uint32_t), hipMemcpyDeviceToHost, T.stream),
                       "pairs_banded runs copy");
             check(hipStreamSynchronize(T.stream), "pairs_banded synchronize");
-            S.dir_ms += elapsed(0);
-            S.walk_ms += elapsed(1);
+            S.dir_ms += banded_elapsed(0);
+            S.walk_ms += banded_elapsed(1);
             S.launches += 2;
 
             // ---- region and text

@@ -1,0 +1,77 @@
+// pairs_banded_host.h -- the host side of the banded pair calls that the local
+// pair calls share (defined in pairs_banded.cpp; used by pairs_local.cpp): the
+// band's clamp and validity rule, the batch ordered by shape and band with its
+// BandStrip ranges, the chunk packer and the device buffers it fills.  Host
+// code only.
+#pragma once
+#include <vector>
+
+#include "pairs_banded.h"
+#include "pairs_host.h"
+
+namespace ssa {
+
+// Band values beyond [-qlen - 1, dlen + 1] are equivalent to the clamped ones.
+int64_t clamp_band(int64_t k, uint64_t ql, uint64_t dl);
+// The header's rule: an interval that meets the start and the end diagonals of the mask.
+bool band_valid(int ends, int64_t m, int64_t n, int64_t lo, int64_t hi);
+
+constexpr size_t kBandScoreChunkBudget = (size_t)256 << 20;   // ssa_amd_score_pairs'
+constexpr size_t kBandAlignChunkBudget = (size_t)2 << 30;     // ssa_amd_align_pairs_ends'
+constexpr size_t kBandPairDirBudget = (size_t)512 << 20;      // direction bits of one pair alone
+constexpr size_t kBandDirRowBytes = 1024;                     // one 64-lane uint4 row of direction bits
+
+// The buffers of the banded and the local calls (one call runs at a time), kept between calls.
+struct BandedDevice {
+    int device = -1;
+    hipEvent_t ev[4] = {};
+    bool events = false;
+    PairsBuf up, bnd, dir, runs, out;
+    PairsBuf stop;                      // the local calls' STOP bits (pairs_local.h)
+};
+BandedDevice& banded_device();
+void banded_prepare_device(int dev_id);
+// milliseconds between the events e and e + 1
+double banded_elapsed(int e);
+
+// 64-lane rows of direction bits a pair needs when it is alone in its group (an upper bound)
+uint64_t pair_dir_rows(uint64_t ql, uint64_t dl, int64_t lo, int64_t hi);
+
+// The device pairs of a call, ordered by shape and band and cut into groups of 64.
+struct BandBatch {
+    const uint8_t* qc;
+    const uint64_t* qoff;
+    const uint8_t* dc;
+    const uint64_t* doff;
+    const int64_t* lo;                  // clamped, by input index
+    const int64_t* hi;
+    std::vector<uint32_t> idx;          // by input index
+    std::vector<BandGroup> groups;
+    std::vector<BandStrip> strips;      // all groups'; BandGroup::s_row is global until a chunk is cut
+    std::vector<uint64_t> drows;        // direction rows of each group
+    std::vector<size_t> gbytes;         // device bytes of each group
+
+    uint32_t qlen(size_t i) const { return (uint32_t)(qoff[i + 1] - qoff[i]); }
+    uint32_t dlen(size_t i) const { return (uint32_t)(doff[i + 1] - doff[i]); }
+    uint32_t nstrips(size_t i) const { return (qlen(i) + kPairsRows - 1) / kPairsRows; }
+
+    // Orders the pairs (strip count, then lo, then hi), cuts the groups and their strips' ranges; row_bytes:
+    // what the align call keeps per 64-lane row of a swept block.  Returns the cells the waves walk.
+    uint64_t order(bool align, size_t row_bytes = kBandDirRowBytes);
+};
+
+// One chunk: groups [g0, g1) laid out in the upload block, packed and uploaded.
+struct BandChunk {
+    size_t g0, g1, ng, nl, p0, p1;
+    uint64_t drow = 0;                  // the align call: 64-lane rows of direction bits
+    uint64_t nruns = 0;                 //   and run slots
+    AlignLane* lanes = nullptr;         //   the host copy of the lanes
+    BandedArgs A{};
+};
+
+// Cuts the chunk that starts at g0 (within the byte budget, at least one
+// group), packs it lane-interleaved into the pinned block and enqueues its
+// upload; sizes every device buffer banded_kernel and banded_walk_kernel touch.
+BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const EndsRouting& T);
+
+}  // namespace ssa
