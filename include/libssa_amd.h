@@ -111,6 +111,9 @@ typedef struct {
     double host_ms;        /* host wall time of the exact host path */
     int32_t device;        /* HIP device of the call, -1: none used */
     char kernel[32];       /* "pairs_sw_i32" / "pairs_nw_i32" */
+    double gather_ms;      /* ssa_amd_score_pairs_indexed on its gather path: HIP-event time of the
+                              pairs_gather_kernel launches (they count in `launches`); else 0 */
+    uint64_t pool_bytes;   /* ... and the bytes of sequence pool the call uploaded; else 0 */
 } ssa_amd_pairs_stats_t;
 
 /* One pair's result of ssa_amd_align_pairs. */
@@ -391,6 +394,38 @@ int ssa_amd_score_pairs( int algo, const uint8_t * q_codes, const uint64_t * q_o
                          const uint8_t * d_codes, const uint64_t * d_off,
                          size_t npairs, int64_t * scores );
 void ssa_amd_get_pairs_stats( ssa_amd_pairs_stats_t * out );
+/* ssa_amd_score_pairs for a list of index pairs over two sequence SETS: the
+ * caller keeps each sequence once, however many pairs it appears in.
+ * q_off has nq + 1 entries and d_off nd + 1; sequence a of the q set is
+ * q_codes[q_off[a] .. q_off[a+1]), likewise for d.  Pair p is q sequence
+ * q_idx[p] against d sequence d_idx[p], and scores[p] is exactly what
+ * ssa_amd_score_pairs writes for that pair in the expanded list (SW and NW,
+ * M[d][q], the empty-side values, the host path for what int32 cannot score).
+ * Duplicate pairs, unreferenced sequences and one set against itself
+ * (q_codes == d_codes) are fine.
+ * Returns 0, or non-zero (nothing written, nothing launched) for an unknown
+ * algo, a NULL argument with npairs > 0, decreasing offsets anywhere in
+ * either set, a code >= 32 anywhere in either pool q_codes[q_off[0] ..
+ * q_off[nq]) / d_codes[d_off[0] .. d_off[nd]) -- the WHOLE pool is checked,
+ * sequences no pair references included, because the whole pool is uploaded
+ * -- or an index q_idx[p] >= nq / d_idx[p] >= nd.  npairs == 0 returns 0.
+ * By default nothing is expanded or interleaved on the host: both pools go to
+ * the device once per call (once in all when q_codes == d_codes, q_off ==
+ * d_off and nq == nd), each pair costs a 24-byte descriptor, and
+ * pairs_gather_kernel writes pairs_kernel's lane-interleaved input on the
+ * device in front of it.  Device choice, stream, "pairs_chunk", "pairs_host"
+ * and ssa_amd_get_pairs_stats are ssa_amd_score_pairs'; on the gather path
+ * `launches` counts both kernels (2 per chunk), pack_ms is the ordering and
+ * the descriptor fill, gather_ms and pool_bytes are set.  Options:
+ *   "pairs_gather" 1|0   1 (default): as above; 0: the pairs are packed on the host, as
+ *                        ssa_amd_score_pairs packs them (same scores; gather_ms = pool_bytes = 0)
+ *   "pairs_pool_mb" N    (default 1024) uploaded pools above N MiB: pack on the host, as under
+ *                        "pairs_gather" 0 */
+int ssa_amd_score_pairs_indexed( int algo,
+                                 const uint8_t * q_codes, const uint64_t * q_off, size_t nq,
+                                 const uint8_t * d_codes, const uint64_t * d_off, size_t nd,
+                                 const uint32_t * q_idx, const uint32_t * d_idx, size_t npairs,
+                                 int64_t * scores );
 /* Region and CIGAR of npairs independent pairs in one call: for every pair
  * (region, CIGAR) is exactly what ssa_amd_align_pair returns for it under the
  * current matrix and gap penalties -- a zero-score SW pair gives (0, 0, 0, 0)

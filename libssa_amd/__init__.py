@@ -80,7 +80,8 @@ class ssa_amd_pairs_stats_t(Structure):
     _fields_ = [("pairs", c_uint64), ("cells", c_uint64), ("swept_cells", c_uint64), ("host_pairs", c_uint64),
                 ("groups", c_uint32), ("chunks", c_uint32), ("launches", c_uint32), ("strip_rows", c_uint32),
                 ("total_ms", c_double), ("pack_ms", c_double), ("kernel_ms", c_double), ("host_ms", c_double),
-                ("device", c_int32), ("kernel", ctypes.c_char * 32)]
+                ("device", c_int32), ("kernel", ctypes.c_char * 32), ("gather_ms", c_double),
+                ("pool_bytes", c_uint64)]
 
 
 class ssa_amd_pair_alignment_t(Structure):
@@ -117,7 +118,7 @@ EXPORTS = {
                       "ssa_amd_map_residues", "ssa_amd_align_pairs", "ssa_amd_get_align_pairs_stats",
                       "ssa_amd_score_pairs_ends", "ssa_amd_align_pairs_ends",
                       "ssa_amd_score_pairs_banded", "ssa_amd_align_pairs_banded",
-                      "ssa_amd_score_pairs_local", "ssa_amd_align_pairs_local"],
+                      "ssa_amd_score_pairs_local", "ssa_amd_align_pairs_local", "ssa_amd_score_pairs_indexed"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -169,6 +170,8 @@ def load():
         "ssa_amd_dist_ranks": ([], c_int),
         "ssa_amd_score_pairs": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
         "ssa_amd_get_pairs_stats": ([POINTER(ssa_amd_pairs_stats_t)], None),
+        "ssa_amd_score_pairs_indexed": ([c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p,
+                                         c_void_p, c_size_t, c_void_p], c_int),
         "ssa_amd_align_pairs": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                                  c_size_t], c_int),
         "ssa_amd_get_align_pairs_stats": ([POINTER(ssa_amd_align_pairs_stats_t)], None),
@@ -428,6 +431,50 @@ def score_pairs_flat(algo, q_codes, q_off, d_codes, d_off):
     arrays and uint64 offset arrays of npairs + 1 entries each (no per-call
     concatenation: what a caller with many pairs keeps around)."""
     return _score_flat("ssa_amd_score_pairs", "score_pairs_flat", algo, q_codes, q_off, d_codes, d_off)
+
+
+def score_pairs_indexed(algo, queries, targets, q_idx, d_idx):
+    """ssa_amd_score_pairs_indexed: the exact score of queries[q_idx[p]]
+    against targets[d_idx[p]] for every p, as an int64 array -- what
+    score_pairs gives for the expanded lists.  queries and targets are lists
+    of uint8 residue-code arrays (the same list object for a set against
+    itself: it is then uploaded once), q_idx and d_idx equal-length integer
+    arrays.  Raises ValueError when the library refuses the arguments."""
+    q, qo = _concat_codes(queries)
+    d, do = (q, qo) if targets is queries else _concat_codes(targets)
+    return score_pairs_indexed_flat(algo, q, qo, d, do, q_idx, d_idx)
+
+
+def score_pairs_indexed_flat(algo, q_codes, q_off, d_codes, d_off, q_idx, d_idx):
+    """ssa_amd_score_pairs_indexed on the C layout itself: contiguous uint8
+    pools, uint64 offset arrays of nq + 1 and nd + 1 entries, and two index
+    arrays of npairs entries (any integer type; values outside uint32 are
+    refused here)."""
+    import numpy as np
+    name = "score_pairs_indexed_flat"
+    for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
+        if a.dtype != t or not a.flags.c_contiguous:
+            raise ValueError(f"{name}: contiguous uint8 codes and uint64 offsets expected")
+    if len(q_off) < 1 or len(d_off) < 1:
+        raise ValueError(f"{name}: offset arrays of nq + 1 and nd + 1 entries expected")
+    idx = []
+    for a in (q_idx, d_idx):
+        a = np.asarray(a)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError(f"{name}: one-dimensional integer index arrays expected")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xffffffff):
+            raise ValueError(f"{name}: an index outside uint32")
+        idx.append(np.ascontiguousarray(a, np.uint32))
+    if len(idx[0]) != len(idx[1]):
+        raise ValueError(f"{name}: q_idx and d_idx differ in length")
+    n = len(idx[0])
+    out = np.zeros(n, np.int64)
+    rc = load().ssa_amd_score_pairs_indexed(algo, q_codes.ctypes.data, q_off.ctypes.data, len(q_off) - 1,
+                                            d_codes.ctypes.data, d_off.ctypes.data, len(d_off) - 1,
+                                            idx[0].ctypes.data, idx[1].ctypes.data, n, out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ssa_amd_score_pairs_indexed refused its arguments ({rc})")
+    return out
 
 
 def _band_arrays(name, band, n):

@@ -640,6 +640,12 @@ int ssa_amd_score_pairs(int algo, const uint8_t* q_codes, const uint64_t* q_off,
     return score_pairs(algo, q_codes, q_off, d_codes, d_off, npairs, scores);
 }
 
+int ssa_amd_score_pairs_indexed(int algo, const uint8_t* q_codes, const uint64_t* q_off, size_t nq,
+                                const uint8_t* d_codes, const uint64_t* d_off, size_t nd, const uint32_t* q_idx,
+                                const uint32_t* d_idx, size_t npairs, int64_t* scores) {
+    return score_pairs_indexed(algo, q_codes, q_off, nq, d_codes, d_off, nd, q_idx, d_idx, npairs, scores);
+}
+
 void ssa_amd_get_pairs_stats(ssa_amd_pairs_stats_t* out) {
     if (out) *out = pairs_stats();
 }
@@ -753,6 +759,8 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "filter_onepass")) cfg().filter_onepass = (int)value;
     else if (!strcmp(name, "pairs_chunk")) cfg().pairs_chunk = (int)std::max(0L, std::min(value, 1L << 30));
     else if (!strcmp(name, "pairs_host")) cfg().pairs_host = (int)value;
+    else if (!strcmp(name, "pairs_gather")) cfg().pairs_gather = (int)value;
+    else if (!strcmp(name, "pairs_pool_mb")) cfg().pairs_pool_mb = (int)std::max(0L, std::min(value, 1L << 20));
     else if (!strcmp(name, "filter_prefix_regs")) set_filter_prefix_regs((int)value);
     else print_warning("unknown option %s", name);
 }

@@ -83,6 +83,9 @@ struct Config {
                                           // C2 +0.5 %, profiles/r05/ab/lean_events)
     int pairs_chunk = 0;                  // ssa_amd_score_pairs: pairs per pack / launch round; 0: by a byte budget
     int pairs_host = 0;                   // 1: every pair of ssa_amd_score_pairs on the exact host path
+    int pairs_gather = 1;                 // ssa_amd_score_pairs_indexed: 1 (default) packs on the device from the
+                                          // uploaded pools (pairs_gather.hip), 0 packs on the host
+    int pairs_pool_mb = 1024;             // ... and packs on the host when the pools exceed this many MiB
     int topk_prune = 1;                   // SW top-k searches on the pair kernel skip the strip parts of groups
                                           // that can no longer reach the top-k (StripArgs::prune)
     int prune_inplace_pct = 25;           // a pruned search's work unit that cannot be skipped at a part boundary
@@ -196,6 +199,10 @@ void compute_alignments(p_alignment_list L, int algo);
 int score_pairs(int algo, const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off,
                 size_t npairs, int64_t* scores);
 const ssa_amd_pairs_stats_t& pairs_stats();
+// pairs.cpp: ssa_amd_score_pairs_indexed (the same statistics)
+int score_pairs_indexed(int algo, const uint8_t* q_codes, const uint64_t* q_off, size_t nq, const uint8_t* d_codes,
+                        const uint64_t* d_off, size_t nd, const uint32_t* q_idx, const uint32_t* d_idx, size_t npairs,
+                        int64_t* scores);
 // pairs_align.cpp: ssa_amd_align_pairs and its statistics
 int align_pairs(int algo, const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off,
                 size_t npairs, ssa_amd_pair_alignment_t* out, char* cigars, size_t cigar_cap);

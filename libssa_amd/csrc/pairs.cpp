@@ -5,6 +5,9 @@
 // score exactly goes through the int64 recurrences below, in parallel on the
 // host.  The call owns its stream and buffers: an open DB, its device copy,
 // the plan cache and ssa_amd_get_stats are not touched.
+// ssa_amd_score_pairs_indexed is the same routine over index
+// pairs into two sequence sets; by default its device pairs are packed on the
+// device by pairs_gather_kernel (pairs_gather.hip) from the uploaded sets.
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -15,6 +18,7 @@
 #include "engine.h"
 #include "pairs.h"
 #include "pairs_align.h"   // parallel_ranges, interleave: shared with the batch aligner
+#include "pairs_gather.h"  // the indexed call's device-side packer
 
 namespace ssa {
 
@@ -79,8 +83,9 @@ struct PairsDevice {
     int device = -1;
     bool probed = false, usable = false;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {};
-    uint8_t* h_up = nullptr;     // pinned upload block: matrix, groups, lens, qres, tres
+    hipEvent_t ev[3] = {};       // kernel begin, kernel end; [2]: gather begin (the indexed call)
+    uint8_t* h_up = nullptr;     // pinned upload block: matrix, groups, then lens, qres, tres or (the
+                                 // indexed call's gather path) one descriptor per lane
     uint8_t* d_up = nullptr;
     size_t up_cap = 0;
     int2* d_bnd = nullptr;
@@ -88,6 +93,11 @@ struct PairsDevice {
     int32_t* d_out = nullptr;
     int32_t* h_out = nullptr;    // pinned
     size_t out_cap = 0;          // groups
+    // the indexed call's gather path: both pools, and what the gather kernel fills (lens, qres, tres)
+    uint8_t* d_pool = nullptr;
+    size_t pool_cap = 0;
+    uint8_t* d_res = nullptr;
+    size_t res_cap = 0;
 
     void release() {
         if (h_up) (void)hipHostFree(h_up);
@@ -95,6 +105,10 @@ struct PairsDevice {
         if (d_bnd) (void)hipFree(d_bnd);
         if (d_out) (void)hipFree(d_out);
         if (h_out) (void)hipHostFree(h_out);
+        if (d_pool) (void)hipFree(d_pool);
+        if (d_res) (void)hipFree(d_res);
+        d_pool = d_res = nullptr;
+        pool_cap = res_cap = 0;
         h_up = d_up = nullptr;
         d_bnd = nullptr;
         d_out = h_out = nullptr;
@@ -170,36 +184,70 @@ const ssa_amd_pairs_stats_t& pairs_stats() {
 
 void set_pairs_stats(const ssa_amd_pairs_stats_t& s) { g_stats = s; }
 
-int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff, size_t n,
-                int64_t* scores) {
-    const double t0 = now_ms();
-    if (algo != SSA_AMD_SW && algo != SSA_AMD_NW) return 1;
-    const bool nw = algo == SSA_AMD_NW;
-    if (n == 0) {
-        ssa_amd_pairs_stats_t& S = g_stats;
-        S = ssa_amd_pairs_stats_t{};
-        S.strip_rows = kPairsRows;
-        S.device = -1;
-        return 0;
-    }
-    if (!qc || !qoff || !dc || !doff || !scores) return 1;
-    if (!matrix().ready) fatal("Scoring matrix not initialized");
-    for (size_t i = 0; i < n; i++)
-        if (qoff[i + 1] < qoff[i] || doff[i + 1] < doff[i]) return 1;
-    // every residue is a code < 32 (the matrix is 32 x 32)
-    {
-        std::atomic<uint32_t> seen{0};
-        auto scan = [&](const uint8_t* p, size_t len) {
-            parallel_ranges(len, 1 << 20, [&](size_t b, size_t e) {
-                uint8_t acc = 0;
-                for (size_t i = b; i < e; i++) acc |= p[i];
-                seen.fetch_or(acc);
-            });
-        };
-        scan(qc + qoff[0], qoff[n] - qoff[0]);
-        scan(dc + doff[0], doff[n] - doff[0]);
-        if (seen.load() >= (uint32_t)kDim) return 1;
-    }
+namespace {
+
+// ------------------------------------------------------------ pair sources
+// Where pair p's two sequences lie.  Everything behind the argument checks --
+// the device conditions, the ordering, the grouping, the host path, the chunk
+// loop -- sees the batch through one of these (score_source below).
+// q_start / d_start: the sequence's byte in its pool, for the gather path.
+
+// ssa_amd_score_pairs: pair p is the p-th interval of both offset arrays
+struct OffsetPairs {
+    const uint8_t *qc, *dc;
+    const uint64_t *qoff, *doff;
+    const uint8_t* q(size_t p) const { return qc + qoff[p]; }
+    const uint8_t* d(size_t p) const { return dc + doff[p]; }
+    uint64_t qlen(size_t p) const { return qoff[p + 1] - qoff[p]; }
+    uint64_t dlen(size_t p) const { return doff[p + 1] - doff[p]; }
+    uint64_t q_start(size_t p) const { return qoff[p] - qoff[0]; }
+    uint64_t d_start(size_t p) const { return doff[p] - doff[0]; }
+};
+
+// ssa_amd_score_pairs_indexed: pair p is sequence qidx[p] of the q set against didx[p] of the d set
+struct IndexedPairs {
+    const uint8_t *qc, *dc;
+    const uint64_t *qoff, *doff;
+    const uint32_t *qidx, *didx;
+    const uint8_t* q(size_t p) const { return qc + qoff[qidx[p]]; }
+    const uint8_t* d(size_t p) const { return dc + doff[didx[p]]; }
+    uint64_t qlen(size_t p) const { return qoff[qidx[p] + 1] - qoff[qidx[p]]; }
+    uint64_t dlen(size_t p) const { return doff[didx[p] + 1] - doff[didx[p]]; }
+    uint64_t q_start(size_t p) const { return qoff[qidx[p]] - qoff[0]; }
+    uint64_t d_start(size_t p) const { return doff[didx[p]] - doff[0]; }
+};
+
+// The gather path's pools (host side): q_start / d_start count from q and d.
+struct GatherPools {
+    const uint8_t *q, *d;
+    size_t qbytes, dbytes;
+    bool shared;          // one pool for both sides: uploaded once
+};
+
+// every residue of [p, p + len) is a code < 32 (the matrix is 32 x 32)
+bool codes_valid(const uint8_t* p, size_t len) {
+    std::atomic<uint32_t> seen{0};
+    parallel_ranges(len, 1 << 20, [&](size_t b, size_t e) {
+        uint8_t acc = 0;
+        for (size_t i = b; i < e; i++) acc |= p[i];
+        seen.fetch_or(acc);
+    });
+    return seen.load() < (uint32_t)kDim;
+}
+
+void reset_stats() {
+    ssa_amd_pairs_stats_t& S = g_stats;
+    S = ssa_amd_pairs_stats_t{};
+    S.strip_rows = kPairsRows;
+    S.device = -1;
+}
+
+// Scores the n checked pairs of `src`.  pools: the indexed call's sequence
+// pools when its device pairs are to be packed by pairs_gather_kernel, NULL
+// for host packing (always so for ssa_amd_score_pairs).
+template <class Src>
+int score_source(const bool nw, const Src& src, const size_t n, int64_t* scores, const GatherPools* pools,
+                 const double t0) {
     const Config& C = cfg();
     const int64_t* M = matrix().m;
     const int64_t Q = C.gap_open, Ge = C.gap_extend;
@@ -230,7 +278,7 @@ int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t
     {
         uint64_t cells = 0;
         for (size_t i = 0; i < n; i++) {
-            const uint64_t ql = qoff[i + 1] - qoff[i], dl = doff[i + 1] - doff[i];
+            const uint64_t ql = src.qlen(i), dl = src.dlen(i);
             cells += ql * dl;
             if (device && ql && dl && (int64_t)(ql + dl) <= residue_limit && ql + dl < ((uint64_t)1 << 31) &&
                 n <= UINT32_MAX)
@@ -251,10 +299,10 @@ int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t
             std::vector<int64_t> he;
             for (size_t k = b; k < e; k++) {
                 const size_t i = todo[k];
-                const size_t ql = qoff[i + 1] - qoff[i], dl = doff[i + 1] - doff[i];
+                const size_t ql = src.qlen(i), dl = src.dlen(i);
                 if (he.size() < 2 * ql) he.resize(2 * ql);
-                scores[i] = nw ? host_nw(dc + doff[i], dl, qc + qoff[i], ql, M, Q, Ge, he.data())
-                               : host_sw(dc + doff[i], dl, qc + qoff[i], ql, M, Q, Ge, he.data());
+                scores[i] = nw ? host_nw(src.d(i), dl, src.q(i), ql, M, Q, Ge, he.data())
+                               : host_sw(src.d(i), dl, src.q(i), ql, M, Q, Ge, he.data());
             }
         });
     }
@@ -263,8 +311,8 @@ int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t
     // ---- the device path
     if (!dev_idx.empty()) {
         PairsDevice& P = g_dev;
-        auto qlen = [&](uint32_t i) { return (uint32_t)(qoff[i + 1] - qoff[i]); };
-        auto dlen = [&](uint32_t i) { return (uint32_t)(doff[i + 1] - doff[i]); };
+        auto qlen = [&](uint32_t i) { return (uint32_t)src.qlen(i); };
+        auto dlen = [&](uint32_t i) { return (uint32_t)src.dlen(i); };
         auto strips = [&](uint32_t i) { return (qlen(i) + kPairsRows - 1) / kPairsRows; };
         // a wave sweeps (most strips) x (most columns) of its 64 pairs: order by both, longest first
         // (the last waves of a launch are then the short ones)
@@ -302,6 +350,28 @@ int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t
         for (int q = 0; q < kDim; q++)
             for (int d = 0; d < kDim; d++) mt[q * 32 + d] = (int8_t)M[(d << 5) + q];
 
+        // ---- the gather path: both pools to the device, once per call, each with readable padding behind it
+        const uint8_t *d_qpool = nullptr, *d_dpool = nullptr;
+        if (pools) {
+            const size_t q_room = align_up(pools->qbytes + kGatherPoolPad);
+            const size_t d_room = pools->shared ? 0 : align_up(pools->dbytes + kGatherPoolPad);
+            if (P.pool_cap < q_room + d_room) {
+                if (P.d_pool) check(hipFree(P.d_pool), "hipFree");
+                P.d_pool = nullptr;
+                P.pool_cap = q_room + d_room + (q_room + d_room) / 4;
+                check(hipMalloc((void**)&P.d_pool, P.pool_cap), "pairs pools");
+            }
+            d_qpool = P.d_pool;
+            d_dpool = pools->shared ? P.d_pool : P.d_pool + q_room;
+            if (pools->qbytes)
+                check(hipMemcpyAsync(P.d_pool, pools->q, pools->qbytes, hipMemcpyHostToDevice, P.stream),
+                      "pairs pool upload");
+            if (!pools->shared && pools->dbytes)
+                check(hipMemcpyAsync(P.d_pool + q_room, pools->d, pools->dbytes, hipMemcpyHostToDevice, P.stream),
+                      "pairs pool upload");
+            S.pool_bytes = pools->qbytes + (pools->shared ? 0 : pools->dbytes);
+        }
+
         const size_t chunk_groups = C.pairs_chunk > 0 ? std::max<size_t>(1, (size_t)C.pairs_chunk / 64) : SIZE_MAX;
         for (size_t g0 = 0; g0 < ngroups;) {
             // ---- the chunk: groups [g0, g1) within the byte budget (at least one)
@@ -325,11 +395,22 @@ int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t
             const size_t ng = g1 - g0;
             const size_t o_mt = 0;
             const size_t o_groups = align_up(sizeof mt);
+            // host packing: lens, qres and tres follow in the upload block; gather path: the upload
+            // block ends with one descriptor per lane, and the three lie in d_res, device memory only
             const size_t o_lens = o_groups + align_up(ng * sizeof(PairsGroup));
-            const size_t o_q = o_lens + align_up(ng * 64 * sizeof(uint2));
+            const size_t o_desc = o_lens;
+            const size_t lens_bytes = align_up(ng * 64 * sizeof(uint2));
+            const size_t o_q = pools ? lens_bytes : o_lens + lens_bytes;
             const size_t o_t = o_q + (size_t)qrow * 256;
-            const size_t up_bytes = o_t + (size_t)trow * 256;
+            const size_t res_end = o_t + (size_t)trow * 256;
+            const size_t up_bytes = pools ? o_desc + ng * 64 * sizeof(PairsDesc) : res_end;
             const size_t bnd_bytes = (size_t)brow * 512;
+            if (pools && P.res_cap < res_end) {
+                if (P.d_res) check(hipFree(P.d_res), "hipFree");
+                P.d_res = nullptr;
+                P.res_cap = res_end + res_end / 4;
+                check(hipMalloc((void**)&P.d_res, P.res_cap), "pairs residues");
+            }
             if (P.up_cap < up_bytes) {
                 if (P.h_up) check(hipHostFree(P.h_up), "hipHostFree");
                 if (P.d_up) check(hipFree(P.d_up), "hipFree");
@@ -356,10 +437,10 @@ int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t
             // ---- pack, lane-interleaved
             memcpy(P.h_up + o_mt, mt, sizeof mt);
             memcpy(P.h_up + o_groups, &groups[g0], ng * sizeof(PairsGroup));
-            uint2* h_lens = (uint2*)(P.h_up + o_lens);
-            uint8_t* h_q = P.h_up + o_q;
-            uint8_t* h_t = P.h_up + o_t;
-            parallel_ranges(ng, 1, [&](size_t b, size_t e) {
+            auto pack_groups = [&](size_t b, size_t e) {
+                uint2* h_lens = (uint2*)(P.h_up + o_lens);
+                uint8_t* h_q = P.h_up + o_q;
+                uint8_t* h_t = P.h_up + o_t;
                 for (size_t g = g0 + b; g < g0 + e; g++) {
                     const PairsGroup& G = groups[g];
                     uint8_t* tq = h_q + (size_t)G.q_row * 256;
@@ -376,27 +457,59 @@ int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t
                         const uint32_t i = dev_idx[p];
                         const uint32_t ql = qlen(i), dl = dlen(i);
                         L = make_uint2(ql, dl);
-                        const uint8_t* qs = qc + qoff[i];
-                        const uint8_t* ds = dc + doff[i];
+                        const uint8_t* qs = src.q(i);
+                        const uint8_t* ds = src.d(i);
                         interleave(tq + l * 4, qs, ql);
                         interleave(tt + l * 4, ds, dl);
                     }
                 }
-            });
+            };
+            if (pools) {
+                // (the gather path: a descriptor per lane; an unused lane's is all zero)
+                PairsDesc* h_desc = (PairsDesc*)(P.h_up + o_desc);
+                parallel_ranges(ng * 64, 1 << 14, [&](size_t b, size_t e) {
+                    for (size_t l = b; l < e; l++) {
+                        const size_t p = g0 * 64 + l;
+                        if (p >= dev_idx.size()) {
+                            h_desc[l] = PairsDesc{0, 0, 0, 0};
+                            continue;
+                        }
+                        const uint32_t i = dev_idx[p];
+                        h_desc[l] = PairsDesc{src.q_start(i), src.d_start(i), qlen(i), dlen(i)};
+                    }
+                });
+            } else {
+                parallel_ranges(ng, 1, pack_groups);
+            }
             S.pack_ms += now_ms() - tc0;
             // ---- upload, score, copy back
             check(hipMemcpyAsync(P.d_up, P.h_up, up_bytes, hipMemcpyHostToDevice, P.stream), "pairs upload");
             PairsArgs A;
             A.mt = (const int8_t*)(P.d_up + o_mt);
             A.groups = (const PairsGroup*)(P.d_up + o_groups);
-            A.lens = (const uint2*)(P.d_up + o_lens);
-            A.qres = (const uint32_t*)(P.d_up + o_q);
-            A.tres = (const uint32_t*)(P.d_up + o_t);
+            A.lens = (const uint2*)(pools ? P.d_res : P.d_up + o_lens);
+            A.qres = (const uint32_t*)((pools ? P.d_res : P.d_up) + o_q);
+            A.tres = (const uint32_t*)((pools ? P.d_res : P.d_up) + o_t);
             A.bnd = P.d_bnd;
             A.out = P.d_out;
             A.gap_open = (int32_t)Q;
             A.gap_extend = (int32_t)Ge;
             A.ngroups = (uint32_t)ng;
+            if (pools) {
+                // lens, qres and tres of the chunk, written on the device; the launch order is the dependency
+                GatherArgs T;
+                T.desc = (const PairsDesc*)(P.d_up + o_desc);
+                T.groups = A.groups;
+                T.qpool = d_qpool;
+                T.dpool = d_dpool;
+                T.qres = (uint32_t*)(P.d_res + o_q);
+                T.tres = (uint32_t*)(P.d_res + o_t);
+                T.lens = (uint2*)P.d_res;
+                T.ngroups = (uint32_t)ng;
+                check(hipEventRecord(P.ev[2], P.stream), "hipEventRecord");
+                check(launch_pairs_gather(T, P.stream), "pairs_gather_kernel");
+                S.launches++;
+            }
             check(hipEventRecord(P.ev[0], P.stream), "hipEventRecord");
             check(launch_pairs(nw ? 1 : 0, A, P.stream), "pairs_kernel");
             check(hipEventRecord(P.ev[1], P.stream), "hipEventRecord");
@@ -406,6 +519,10 @@ int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t
             float ms = 0;
             check(hipEventElapsedTime(&ms, P.ev[0], P.ev[1]), "hipEventElapsedTime");
             S.kernel_ms += ms;
+            if (pools) {
+                check(hipEventElapsedTime(&ms, P.ev[2], P.ev[0]), "hipEventElapsedTime");
+                S.gather_ms += ms;
+            }
             for (size_t p = g0 * 64; p < std::min(dev_idx.size(), g1 * 64); p++)
                 scores[dev_idx[p]] = P.h_out[p - g0 * 64];
             S.chunks++;
@@ -416,6 +533,60 @@ int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t
     S.total_ms = now_ms() - t0;
     g_stats = S;
     return 0;
+}
+
+}  // namespace
+
+int score_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff, size_t n,
+                int64_t* scores) {
+    const double t0 = now_ms();
+    if (algo != SSA_AMD_SW && algo != SSA_AMD_NW) return 1;
+    if (n == 0) {
+        reset_stats();
+        return 0;
+    }
+    if (!qc || !qoff || !dc || !doff || !scores) return 1;
+    if (!matrix().ready) fatal("Scoring matrix not initialized");
+    for (size_t i = 0; i < n; i++)
+        if (qoff[i + 1] < qoff[i] || doff[i + 1] < doff[i]) return 1;
+    if (!codes_valid(qc + qoff[0], qoff[n] - qoff[0]) || !codes_valid(dc + doff[0], doff[n] - doff[0])) return 1;
+    return score_source(algo == SSA_AMD_NW, OffsetPairs{qc, dc, qoff, doff}, n, scores, nullptr, t0);
+}
+
+int score_pairs_indexed(int algo, const uint8_t* qc, const uint64_t* qoff, size_t nq, const uint8_t* dc,
+                        const uint64_t* doff, size_t nd, const uint32_t* qidx, const uint32_t* didx, size_t n,
+                        int64_t* scores) {
+    const double t0 = now_ms();
+    if (algo != SSA_AMD_SW && algo != SSA_AMD_NW) return 1;
+    if (n == 0) {
+        reset_stats();
+        return 0;
+    }
+    if (!qc || !qoff || !dc || !doff || !qidx || !didx || !scores) return 1;
+    if (!matrix().ready) fatal("Scoring matrix not initialized");
+    // both sets whole, referenced by a pair or not: the gather path uploads them as they are
+    for (size_t a = 0; a < nq; a++)
+        if (qoff[a + 1] < qoff[a]) return 1;
+    for (size_t b = 0; b < nd; b++)
+        if (doff[b + 1] < doff[b]) return 1;
+    const bool shared = qc == dc && qoff == doff && nq == nd;
+    const size_t qbytes = qoff[nq] - qoff[0], dbytes = doff[nd] - doff[0];
+    if (!codes_valid(qc + qoff[0], qbytes) || (!shared && !codes_valid(dc + doff[0], dbytes))) return 1;
+    {
+        std::atomic<bool> outside{false};
+        parallel_ranges(n, 1 << 18, [&](size_t b, size_t e) {
+            bool bad = false;
+            for (size_t p = b; p < e; p++) bad |= qidx[p] >= nq || didx[p] >= nd;
+            if (bad) outside.store(true);
+        });
+        if (outside.load()) return 1;
+    }
+    const Config& C = cfg();
+    const IndexedPairs src{qc, dc, qoff, doff, qidx, didx};
+    const GatherPools pools{qc + qoff[0], dc + doff[0], qbytes, dbytes, shared};
+    const uint64_t uploaded = (uint64_t)qbytes + (shared ? 0 : dbytes);
+    const bool gather = C.pairs_gather && uploaded <= (uint64_t)std::max(0, C.pairs_pool_mb) << 20;
+    return score_source(algo == SSA_AMD_NW, src, n, scores, gather ? &pools : nullptr, t0);
 }
 
 }  // namespace ssa
