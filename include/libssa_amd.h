@@ -183,6 +183,12 @@ int ssa_amd_set_devices( const int * devices, int n );
 int ssa_amd_get_devices( int * out, int cap );
 int ssa_amd_prepare_db( void );            /* pack + upload the DB now; returns 0 on success */
 void ssa_amd_get_stats( ssa_amd_stats_t * out );
+/* One more figure of the last search, beside ssa_amd_stats_t (whose layout is
+ * kept as it is): the work units of a pruned search skipped before their first
+ * part because no entry of theirs is long enough to reach the top-k threshold
+ * (option "prune_len"); their later units return at once and are not counted in
+ * pruned_units.  A batch reports the sum. */
+uint32_t ssa_amd_get_pruned_whole( void );
 /* Tuning knobs (results never change, only which kernel computes them):
  *   "strip_np" 8|16|32   int16 strip kernels: packed rows per strip
  *   "pair_np" 0|16|24|32|36|40  pair kernel main strip of 2 x pair_np rows; 0 (default):
@@ -251,6 +257,12 @@ void ssa_amd_get_stats( ssa_amd_stats_t * out );
  *                        its remaining parts itself, at once, when its best entry so far has reached
  *                        N % (default 25) of the most the query rows so far can score; 0: never.
  *                        Changes the schedule only, never a score (stats inplace_units)
+ *   "prune_len" 1|0      1 (default): a pruned search skips a whole work unit, before its first row, when
+ *                        none of its entries is long enough to reach the current k-th best score
+ *                        (ssa_amd_get_pruned_whole); hits are identical
+ *   "prune_order" 1|0    1 (default): a pruned search starts the work units whose entry lengths lie
+ *                        within "prune_order_pct" % (default 25) of the query's length alternately
+ *                        with the longest ones, instead of longest first (only with "prune_len" on).  The schedule only
  *   "rare_merge" 0|1     1 (default 0): when a query's residue classes leave the pair table too big
  *                        for three workgroups per CU, the rarest classes share one class scoring
  *                        the maximum of their rows, and the entries holding them that the device
@@ -281,6 +293,18 @@ void ssa_amd_set_option( const char * name, long value );
  * (may be NULL) and returns the row count.  A profiling aid (tools/timeline.py),
  * not part of the reference's interface. */
 size_t ssa_amd_get_timeline( uint32_t * out, size_t cap );
+
+/* The order in which a pruned search (option "topk_prune") starts its first
+ * work units (option "prune_order"), as the library plans it: ncols[ngroups]
+ * are the column counts of the launch's 64-entry groups, longest first, a unit
+ * is four consecutive groups, qlen the query's length and pct the window
+ * (option "prune_order_pct"), of which at most `most` units, the nearest to qlen,
+ * are moved ahead (0: all; a search passes half of what the device holds at
+ * once).  Writes at most cap unit indices to out (may be
+ * NULL) and returns the unit count.  Host code only: no device, no DB.  A
+ * testing aid, not part of the reference's interface. */
+size_t ssa_amd_prune_start_order( const uint32_t * ncols, size_t ngroups, size_t qlen, unsigned pct,
+                                  unsigned most, uint32_t * out, size_t cap );
 
 /* Scores the open DB against the query.  mode: SSA_AMD_TOPK or SSA_AMD_LOG.
  * Returns the number of hits written (at most cap; the log never exceeds

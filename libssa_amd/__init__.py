@@ -118,7 +118,8 @@ EXPORTS = {
                       "ssa_amd_map_residues", "ssa_amd_align_pairs", "ssa_amd_get_align_pairs_stats",
                       "ssa_amd_score_pairs_ends", "ssa_amd_align_pairs_ends",
                       "ssa_amd_score_pairs_banded", "ssa_amd_align_pairs_banded",
-                      "ssa_amd_score_pairs_local", "ssa_amd_align_pairs_local", "ssa_amd_score_pairs_indexed"],
+                      "ssa_amd_score_pairs_local", "ssa_amd_align_pairs_local", "ssa_amd_score_pairs_indexed",
+                      "ssa_amd_prune_start_order", "ssa_amd_get_pruned_whole"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -166,6 +167,9 @@ def load():
         "ssa_amd_merge_logs": ([POINTER(ssa_hit_t), POINTER(c_size_t), c_size_t, c_size_t, c_size_t,
                                 POINTER(ssa_hit_t)], c_size_t),
         "ssa_amd_get_timeline": ([c_void_p, c_size_t], c_size_t),
+        "ssa_amd_get_pruned_whole": ([], ctypes.c_uint32),
+        "ssa_amd_prune_start_order": ([c_void_p, c_size_t, c_size_t, ctypes.c_uint, ctypes.c_uint, c_void_p, c_size_t],
+                                      c_size_t),
         "ssa_amd_dist_available": ([], c_int), "ssa_amd_dist_init_fake": ([c_int, c_int, c_int], c_int),
         "ssa_amd_dist_ranks": ([], c_int),
         "ssa_amd_score_pairs": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
@@ -312,6 +316,7 @@ def stats():
     s = ssa_amd_stats_t()          # (per call: threads of a fake dist group read their own)
     load().ssa_amd_get_stats(ctypes.byref(s))
     d = {f: getattr(s, f) for f, _ in ssa_amd_stats_t._fields_}
+    d["pruned_whole"] = int(load().ssa_amd_get_pruned_whole())    # (beside the struct, whose layout is kept)
     d["kernel"] = d["kernel"].decode()
     d["long_kernel"] = d["long_kernel"].decode()
     n = d["slots"]
@@ -330,6 +335,19 @@ def timeline():
     out = np.zeros((n, 4), np.uint32)
     if n:
         L.ssa_amd_get_timeline(out.ctypes.data, n)
+    return out
+
+
+def prune_start_order(ncols, qlen, pct=25, most=0):
+    """ssa_amd_prune_start_order: the unit each first-part ticket of a pruned
+    search runs, for groups of ncols columns (longest first).  Host only."""
+    import numpy as np
+    nc = np.ascontiguousarray(ncols, np.uint32)
+    L = load()
+    n = L.ssa_amd_prune_start_order(nc.ctypes.data, nc.size, qlen, pct, most, None, 0)
+    out = np.zeros(n, np.uint32)
+    if n:
+        L.ssa_amd_prune_start_order(nc.ctypes.data, nc.size, qlen, pct, most, out.ctypes.data, n)
     return out
 
 

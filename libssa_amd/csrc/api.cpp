@@ -25,6 +25,13 @@ p_query query_from_file(const char* path);
 
 namespace {
 
+// The last search's units skipped whole by length (ssa_amd_get_pruned_whole):
+// kept beside ssa_amd_stats_t, whose layout callers have compiled in.
+uint32_t& pruned_whole_stat() {
+    static uint32_t n = 0;
+    return n;
+}
+
 // The environment's device list as the search uses it: its first
 // set_thread_count() devices -- the reference's thread count is its number of
 // search workers (thread_pool.c:39-47), a device slot's analogue here; 0 (the
@@ -264,12 +271,14 @@ void publish_stats(const std::vector<SearchScores>& sc, const std::vector<SlotPl
     S.part_retries = 0;
     S.rare_merged = S.rare_rescored = 0;
     S.part_units = S.pruned_units = S.inplace_units = S.pruned_first = 0;
+    pruned_whole_stat() = 0;
     for (const SearchScores& x : sc) {
         S.part_retries += x.part_retries;
         S.part_units += x.part_units;
         S.pruned_units += x.pruned_units;
         S.inplace_units += x.inplace_units;
         S.pruned_first += x.pruned_first;
+        pruned_whole_stat() += x.pruned_whole;
         S.rare_merged = std::max(S.rare_merged, x.rare_merged);
         S.rare_rescored += x.rare_rescored;
     }
@@ -308,7 +317,7 @@ void run_search(p_query q, int algo, size_t k, int bw, bool want_log, SearchResu
     TopK heap(k);
     if (plan.size() == 1) {
         replay(sc[0], device_db(0).meta, R.views, heap, want_log ? &R.hits : nullptr);
-        if (sc[0].pruned_units > 0 && heap.tie_evicted()) {
+        if ((sc[0].pruned_units > 0 || sc[0].pruned_whole > 0) && heap.tie_evicted()) {
             // an entry tied at the k-th score left the heap: which of the
             // tied ones stay depends on the heap's layout, and so on the exact
             // scores of entries the pruned search only bounded from below
@@ -603,6 +612,16 @@ size_t ssa_amd_get_timeline(uint32_t* out, size_t cap) {
     return D.timeline_rows;
 }
 
+size_t ssa_amd_prune_start_order(const uint32_t* ncols, size_t ngroups, size_t qlen, unsigned pct, unsigned most,
+                                 uint32_t* out, size_t cap) {
+    if (!ncols || ngroups == 0) return 0;
+    const std::vector<uint32_t> ord = prune_start_order(ncols, (uint32_t)ngroups, qlen, pct, most);
+    if (out) std::copy(ord.begin(), ord.begin() + std::min(cap, ord.size()), out);
+    return ord.size();
+}
+
+uint32_t ssa_amd_get_pruned_whole(void) { return pruned_whole_stat(); }
+
 void ssa_amd_get_stats(ssa_amd_stats_t* out) {
     if (!out) return;
     *out = stats();
@@ -745,6 +764,9 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "rare_merge")) cfg().rare_merge = (int)value;
     else if (!strcmp(name, "topk_prune")) cfg().topk_prune = (int)value;
     else if (!strcmp(name, "prune_inplace_pct")) cfg().prune_inplace_pct = (int)std::min(100L, std::max(0L, value));
+    else if (!strcmp(name, "prune_len")) cfg().prune_len = (int)value;
+    else if (!strcmp(name, "prune_order")) cfg().prune_order = (int)value;
+    else if (!strcmp(name, "prune_order_pct")) cfg().prune_order_pct = (int)std::min(400L, std::max(0L, value));
     else if (!strcmp(name, "sync_spin")) cfg().sync_spin = (int)value;
     else if (!strcmp(name, "lean_events")) cfg().lean_events = (int)value;
     else if (!strcmp(name, "long16_rows")) cfg().long16_rows = (int)value;
@@ -811,7 +833,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         std::iota(ord.begin(), ord.end(), (size_t)0);
         std::stable_sort(ord.begin(), ord.end(),
                          [&](size_t x, size_t y) { return qviews[x][0].len < qviews[y][0].len; });
-        uint32_t launches = 0, retries = 0, punits = 0, pruned = 0, inplace = 0, pfirst = 0;
+        uint32_t launches = 0, retries = 0, punits = 0, pruned = 0, inplace = 0, pfirst = 0, pwhole = 0;
         uint64_t ncand = 0;
         for (size_t b0 = 0; b0 < nq; b0 += kMaxBatchPipe) {
             const size_t b1 = std::min(nq, b0 + kMaxBatchPipe);
@@ -829,6 +851,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
                 pruned += stats().pruned_units;
                 inplace += stats().inplace_units;
                 pfirst += stats().pruned_first;
+                pwhole += pruned_whole_stat();
                 ncand += stats().filter_candidates;
                 launches++;
                 const size_t n = std::min(hitcount, R.hits.size());
@@ -873,6 +896,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         S.pruned_units = pruned;
         S.inplace_units = inplace;
         S.pruned_first = pfirst;
+        pruned_whole_stat() = pwhole;
         S.filter_candidates = ncand;
         S.search_ms = now_ms() - t0;
         S.total_searches = before.total_searches + nq;
@@ -880,7 +904,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         S.total_search_ms = before.total_search_ms + S.search_ms;
         return total;
     }
-    uint32_t retries = 0, launches = 0, punits = 0, pruned = 0, inplace = 0, pfirst = 0;
+    uint32_t retries = 0, launches = 0, punits = 0, pruned = 0, inplace = 0, pfirst = 0, pwhole = 0;
     uint64_t ncand = 0;
     for (size_t i = 0; i < nq; i++) {
         test_configuration(queries[i]);
@@ -893,6 +917,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         pruned += stats().pruned_units;
         inplace += stats().inplace_units;
         pfirst += stats().pruned_first;
+        pwhole += pruned_whole_stat();
         ncand += stats().filter_candidates;
         launches += stats().kernel_launches;
         const size_t n = std::min(hitcount, R.hits.size());
@@ -913,6 +938,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
     S.pruned_units = pruned;
     S.inplace_units = inplace;
     S.pruned_first = pfirst;
+    pruned_whole_stat() = pwhole;
     S.filter_candidates = ncand;
     S.kernel_launches = launches;
     S.search_ms = now_ms() - t0;

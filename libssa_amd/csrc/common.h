@@ -92,6 +92,12 @@ struct Config {
                                           // runs its remaining parts itself, in the same workgroup, when its best
                                           // lane has reached this share (%) of what the rows so far can give at
                                           // most; 0: never (every later part as a work unit of its own)
+    int prune_len = 1;                    // a pruned search skips a whole work unit none of whose entries is long
+                                          // enough to reach the threshold (kernels.h kPruneLen; stats pruned_whole)
+    int prune_order = 1;                  // a pruned search starts the units whose entry lengths lie near the
+                                          // query's alternately with the longest ones (engine.cpp prune_start_order);
+                                          // only with prune_len
+    int prune_order_pct = 25;             // ... within this many % of the query length
     int rare_merge = 0;                   // 1: when the query's residue classes leave the pair table too big for
                                           // three workgroups per CU, the rarest classes share one upper-bound
                                           // class and the forwarded entries holding them are re-scored exactly

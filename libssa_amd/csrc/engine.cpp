@@ -79,6 +79,8 @@ void DeviceDB::release() {
     dfree(d_smax);
     d_part = d_smax = nullptr;
     part_cap = smax_cap = 0;
+    part_quads = part_rows = 0;
+    part_order_key = part_order_key2 = ~0ull;
     dfree(d_rowbuf_q);
     d_rowbuf_q = nullptr;
     rowbuf_q_cap = 0;
@@ -1366,6 +1368,56 @@ bool batch_pipelinable(size_t nqueries, size_t k) {
     return nqueries > 1 && k > 0 && k <= (size_t)kFilterMaxK && !cfg().no_filter;
 }
 
+// The start order of a pruned search's part-0 units (kernels.h kPruneOrd):
+// ticket t runs unit order[t], a unit being kPairWaves consecutive groups of
+// the pair launch (ncols: their column counts, longest first).  Two lists
+// alternate until the second is used up, then the first goes on alone:
+// (a) the units longest first -- the order without this table; (b) the units
+// whose entry lengths meet [m - w, m + w], w = pct % of m, nearest to m first.
+// A query's strong hits have lengths near its own, and a unit with a strong
+// hit finishes in place: it walks all of the query's rows serially, so it is
+// the launch's critical path and the source of the final threshold, and it
+// should start at once.  The R longest units still start within the first 2R
+// tickets.  cap (0: none): list (b) holds at most that many units, the nearest
+// to m -- the caller passes half of what is resident at once, so every
+// candidate and the longest units all start within the first residency wave
+// and the longest-first order behind them is late by half a wave at most (it
+// is what keeps the launch's tail short).  A choice of schedule only.
+std::vector<uint32_t> prune_start_order(const uint32_t* ncols, uint32_t ngroups, size_t m, uint32_t pct, uint32_t cap) {
+    const uint32_t nq = (ngroups + kPairWaves - 1) / kPairWaves;
+    // a unit's entry lengths lie in [lo, hi]: ncols is the longest entry + 1
+    // rounded up to 4, and the next unit's longest entry is no longer than
+    // this one's shortest
+    auto hi = [&](uint32_t u) -> int64_t { return std::max<int64_t>((int64_t)ncols[(size_t)u * kPairWaves] - 1, 0); };
+    auto lo = [&](uint32_t u) -> int64_t { return u + 1 < nq ? std::max<int64_t>(hi(u + 1) - 3, 0) : 0; };
+    const int64_t mm = (int64_t)m, w = mm * pct / 100;
+    std::vector<std::pair<int64_t, uint32_t>> near;
+    for (uint32_t u = 0; u < nq; u++)
+        if (hi(u) >= mm - w && lo(u) <= mm + w) near.push_back({hi(u) < mm ? mm - hi(u) : lo(u) > mm ? lo(u) - mm : 0, u});
+    std::sort(near.begin(), near.end());
+    if (cap != 0 && near.size() > cap) near.resize(cap);
+    std::vector<uint32_t> ord;
+    ord.reserve(nq);
+    std::vector<uint8_t> placed(nq, 0);
+    auto place = [&](uint32_t u) {
+        placed[u] = 1;
+        ord.push_back(u);
+    };
+    uint32_t ia = 0;
+    size_t ib = 0;
+    for (;;) {
+        while (ib < near.size() && placed[near[ib].second]) ib++;
+        if (ib == near.size()) break;
+        while (ia < nq && placed[ia]) ia++;
+        if (ia < nq) place(ia);
+        while (ib < near.size() && placed[near[ib].second]) ib++;
+        if (ib < near.size()) place(near[ib].second);
+    }
+    for (; ia < nq; ia++)
+        if (!placed[ia]) place(ia);
+    return ord;
+}
+
 // One search (device_search below).  no_parts: every group as one work unit
 // (StripArgs::nparts = 1).  Returns false when a strip part's wait for its
 // group's first part ran into its bound (StripArgs::part_wait): the scores
@@ -1394,7 +1446,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     out.cells = 0;
     out.cand.clear();
     out.dev_o8 = out.dev_o16 = 0;
-    out.part_units = out.pruned_units = out.inplace_units = out.pruned_first = 0;
+    out.part_units = out.pruned_units = out.inplace_units = out.pruned_first = out.pruned_whole = 0;
     // the reference's overflow counters (counters.hip): per (view, entry)
     // flags, summed on the device after the last view -- only when someone
     // observes them (m_run prints them at OUTPUT_INFO, manager.c:157-160;
@@ -1780,7 +1832,33 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
         // (+ a fused batch's row counts, view 0: StripArgs::qm)
         const size_t top_bytes = (top.size() * 4 + 15) & ~(size_t)15;
         const size_t qm_off = (kUpHeader + top_bytes + m + 3) & ~(size_t)3;
-        const size_t blk_bytes = (fused && v == 0) ? qm_off + 4 * V : kUpHeader + top_bytes + m;
+        // (+ a search that may be pruned: lenmax[0 .. m], the most an entry of
+        // L residues can score -- the sum of the min(L, m) largest row maxima
+        // of the profile, on the codes the kernel scores with.  A local
+        // alignment uses each DB residue and each query row at most once and
+        // gaps only subtract.  The tables kernel copies it behind the pruning
+        // block, kernels.h kPruneLen)
+        const bool len_want = allow_prune && C.topk_prune && C.prune_len && !nw && V == 1 && !ind && use_pair;
+        std::vector<uint32_t> lenmax;
+        if (len_want) {
+            std::vector<int64_t> rowmax(m);
+            for (size_t i = 0; i < m; i++) {
+                int64_t best = 0;
+                for (uint32_t c = 0; c < A; c++) best = std::max(best, vp.crow[(size_t)c * 32 + qv.seq[i]]);
+                rowmax[i] = best;
+            }
+            std::sort(rowmax.begin(), rowmax.end(), std::greater<int64_t>());
+            lenmax.resize(m + 1);
+            int64_t sum = 0;
+            lenmax[0] = 0;
+            for (size_t i = 0; i < m; i++) {
+                sum = std::min<int64_t>(sum + rowmax[i], 1 << 30);
+                lenmax[i + 1] = (uint32_t)sum;
+            }
+        }
+        const size_t blk_bytes = (fused && v == 0) ? qm_off + 4 * V
+                                 : len_want        ? qm_off + 4 * lenmax.size()
+                                                   : kUpHeader + top_bytes + m;
         const size_t up_bytes = blk_bytes + 16 + qpt.size() * 4;
         // the staging buffer is reused: in a multi-view search the previous
         // view's copies may still be queued behind its predecessor's kernel
@@ -1840,6 +1918,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 const uint32_t mi = (uint32_t)views[i].len;
                 memcpy(up_m + qm_off + 4 * i, &mi, 4);
             }
+        if (len_want) memcpy(up_m + qm_off, lenmax.data(), 4 * lenmax.size());
         if (!qpt.empty()) memcpy(up_q, qpt.data(), qpt.size() * 4);
         if (!lean) check(hipEventRecord(D.ev[4], st), "event");
         if (!qpt.empty())
@@ -2182,17 +2261,61 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     pl_parts = early ? 3u : (T + pl_ps - 1) / pl_ps;
                     // the strip index of each part boundary
                     const uint32_t cuts[2] = {early ? 2u : pl_ps, early ? (T + 1) / 2 : 2 * pl_ps};
-                    if (D.part_cap < pl_quads * nqf) {
+                    want_prune = want_prune && pl_parts > 1;
+                    // (a pruned search: one query, nqf = 1)
+                    // (the start order only with the skip: what it buys is a final tau before
+                    // the short units take their tickets; alone it measured slower than longest first)
+                    const bool want_len = want_prune && len_want, want_ord = want_len && C.prune_order;
+                    if (D.part_cap < pl_quads * nqf || (want_ord && D.part_quads < pl_quads) ||
+                        (want_len && D.part_rows < m + 1)) {
                         // the pruning block, then per quad (and query) its flag
-                        // and bound (kernels.h kPrune*)
+                        // and bound (kernels.h kPrune*), then a pruned search's
+                        // start order and length bounds
                         if (piped && v > 0) check(hipStreamSynchronize(st), "sync");
-                        const size_t bytes = ((size_t)kPruneWords + (size_t)pl_quads * nqf * 2) * 4;
+                        const size_t cap = std::max(D.part_cap, pl_quads * nqf);
+                        const size_t quads = std::max<size_t>(D.part_quads, want_ord ? pl_quads : 0);
+                        const size_t rows = std::max<size_t>(D.part_rows, want_len ? m + 1 + 256 : 0);
+                        const size_t bytes = ((size_t)kPruneWords + cap * 2 + quads + rows) * 4;
                         dfree(D.d_part);
                         check(hipMalloc((void**)&D.d_part, bytes), "strip parts");
                         check(hipMemsetAsync(D.d_part, 0, bytes, st), "memset");
-                        D.part_cap = pl_quads * nqf;
+                        // (the start order is copied in below, not on this stream)
+                        if (want_ord) check(hipStreamSynchronize(st), "sync");
+                        D.part_cap = cap;
+                        D.part_quads = quads;
+                        D.part_rows = rows;
+                        D.part_order_key = D.part_order_key2 = ~0ull;
                     }
-                    want_prune = want_prune && pl_parts > 1;
+                    if (want_prune) {
+                        if (want_ord) {
+                            // the start order, behind the quads' words: rebuilt
+                            // when the split groups, the query's rows or the
+                            // window change (every earlier search has drained
+                            // the stream: a pruned search is not pipelined)
+                            const uint32_t pct = (uint32_t)std::min(std::max(C.prune_order_pct, 0), 400);
+                            // (at most half a residency wave of candidates: the pair
+                            // workgroups one CU holds, by LDS and by registers, x CUs)
+                            const uint32_t ocap = (uint32_t)(std::min<size_t>(pair_wgs_per_cu(pair_lds), 3) * (D.nsimd / 4) / 2);
+                            // (the groups' lengths are not in the key: a repacked DB
+                            // goes through release(), which resets it)
+                            const uint64_t key = (uint64_t)m << 32 | pl_quads,
+                                           key2 = (uint64_t)pct << 52 | (uint64_t)ocap << 32 | long_groups;
+                            if (D.part_order_key != key || D.part_order_key2 != key2) {
+                                const std::vector<uint32_t> ord =
+                                    prune_start_order(D.group_ncols.data() + long_groups, D.ngroups - long_groups, m, pct, ocap);
+                                check(hipMemcpy(D.d_part + kPruneWords + 2 * D.part_cap, ord.data(), ord.size() * 4,
+                                                hipMemcpyHostToDevice), "H2D start order");
+                                D.part_order_key = key;
+                                D.part_order_key2 = key2;
+                            }
+                            ta.prune_ord = (uint32_t)(2 * D.part_cap);
+                        }
+                        if (want_len) {
+                            ta.prune_len = (uint32_t)(2 * D.part_cap + D.part_quads);
+                            ta.prune_len_n = (uint32_t)(m + 1);
+                            ta.prune_lenmax = (const uint32_t*)(dup + qm_off);
+                        }
+                    }
                     ta.prune_blk = D.d_part;
                     if (want_prune) {
                         // rem: what the query rows below a part's last one can
@@ -2737,6 +2860,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 out.pruned_units = D.h_fbuf[4];
                 out.inplace_units = D.h_fbuf[5];
                 out.pruned_first = D.h_fbuf[6];
+                out.pruned_whole = D.h_fbuf[7];
             }
             if (nc > D.cand_first) {
                 more.resize(nc);

@@ -120,6 +120,11 @@ struct DeviceDB {
     // parts done and pruning bound; per lane running maxima
     uint32_t* d_part = nullptr;
     size_t part_cap = 0;
+    // ... behind the quads' words: a pruned search's start order (one unit per
+    // part-0 ticket; kept while its key -- split groups, query rows, window --
+    // stays), then its length bounds (kernels.h kPruneOrd, kPruneLen)
+    size_t part_quads = 0, part_rows = 0; // what the allocation was sized for
+    uint64_t part_order_key = ~0ull, part_order_key2 = ~0ull;
     uint32_t part_epoch = 0;              // the last pair launch's handoff flag value (StripArgs::part_epoch)
     // the long-entry dispatch gate (d_cnt's gate word) is never cleared per
     // search: it counts every long workgroup launched since d_cnt was last
@@ -228,6 +233,7 @@ struct SearchScores {
     uint32_t part_units = 0, pruned_units = 0;
     // ... the units that ran their remaining parts in place, and the skipped ones of the first part boundary
     uint32_t inplace_units = 0, pruned_first = 0;
+    uint32_t pruned_whole = 0;           // units skipped before their first part (no entry long enough)
     int64_t get(size_t v, size_t e) const {
         const int32_t x = s32[v * entries + e];
         if (x != INT32_MIN) return x;
@@ -247,6 +253,8 @@ struct SearchScores {
 void device_search(DeviceDB& D, const std::vector<QueryView>& views, int algo, size_t k, int bw, SearchScores& out,
                    std::vector<SearchScores>* indep = nullptr, bool allow_prune = false);
 bool batch_pipelinable(size_t nqueries, size_t k);
+// engine.cpp: part-0 ticket -> unit of a pruned search (option "prune_order")
+std::vector<uint32_t> prune_start_order(const uint32_t* ncols, uint32_t ngroups, size_t m, uint32_t pct, uint32_t cap);
 constexpr size_t kMaxBatchPipe = 16;    // queries per pipelined sub-batch (one fused launch when their plans agree)
 static_assert(kMaxBatchPipe == (size_t)kMaxFuse, "a sub-batch fuses into one pair_kernel launch");
 

@@ -160,14 +160,23 @@ struct StripArgs {
 //     part whose bound is not below tau yet waits, bounded, for tau's final
 //     value (the units in place are resident, so they end regardless);
 //   cut[2]: the strip index of the first and second part boundary of a plan
-//     with unequal parts (0: StripArgs::part_strips strips each).
+//     with unequal parts (0: StripArgs::part_strips strips each);
+//   len, whole: the dword offset from part_done of lenmax[0 .. m] (0: none;
+//     option "prune_len"), lenmax[L] the most an entry of L residues can score
+//     against this query; a part-0 unit whose longest entry has lenmax below tau
+//     stores 0 for its lanes and runs nothing -- and how many units did;
+//   ord: the dword offset from part_done of the start order (0: none; option
+//     "prune_order"): part-0 ticket t runs quad order[t], a permutation of the
+//     quads.  Later parts' tickets are unchanged, so every part-0 ticket still
+//     precedes every later part's.
 // Every part but the last publishes as its quad's bound the most any of the
 // quad's entries can still score below its last row i_b: max over lanes of
 // max_j H(i_b, j), plus rem.  A later part whose bound is below tau writes its
 // lanes' maxima so far as their scores and returns.
 constexpr uint32_t kPruneLock = 0, kPruneTau = 1, kPruneCount = 2, kPruneK = 3, kPruneRem = 4, kPruneLock2 = 6,
                    kPruneInplace = 7, kPruneFirst = 8, kPruneProm = 9, kPruneCut = 11, kPruneInplaceWaves = 13,
-                   kPruneInplaceDone = 14, kPruneList = 16,
+                   kPruneInplaceDone = 14, kPruneWhole = 15, kPruneLen = 16, kPruneOrd = 17,
+                   kPruneList = 24,
                    kPruneList2 = kPruneList + 64, kPruneWords = kPruneList2 + 64;
 // bound values above every score: never skip (a lane the part-0 maximum leaves
 // undecided) / an earlier part of the quad was skipped / the earlier part's
@@ -317,7 +326,7 @@ struct FilterArgs {
     uint32_t epoch;
     // single view: the pair kernel's skipped-unit count (kPruneCount),
     // copied into counters[4] like status, with kPruneInplace and kPruneFirst
-    // of the same block into counters[5] and [6]; null: none
+    // of the same block into counters[5] and [6], kPruneWhole into [7]; null: none
     const uint32_t* pruned;
 };
 constexpr int kFilterSeqWord = 15;    // header word that carries FilterArgs::host_seq
@@ -477,6 +486,10 @@ struct TableArgs {
     // written by block 0: k, rem, everything else 0; null: none
     uint32_t* prune_blk;
     uint32_t prune_k, prune_rem[2], prune_prom[2], prune_cut[2];
+    // kPruneLen / kPruneOrd as they stand; block 0 copies
+    // prune_lenmax[0 .. prune_len_n) to prune_blk + kPruneWords + prune_len
+    uint32_t prune_len, prune_ord, prune_len_n;
+    const uint32_t* prune_lenmax;
 };
 hipError_t launch_pair_tables(const TableArgs& a, hipStream_t st);
 // dst (device) <- src (pinned host), bytes a multiple of 4: a kernel on st

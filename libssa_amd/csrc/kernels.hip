@@ -766,7 +766,7 @@ __global__ void __launch_bounds__(256) filter_select(const FilterArgs a0) {
     if (tid == 0 && a.pruned) {
         a.counters[4] = *a.pruned;
         a.counters[5] = a.pruned[kPruneInplace - kPruneCount];
-        a.counters[6] = a.pruned[kPruneFirst - kPruneCount];
+        a.counters[6] = a.pruned[kPruneFirst - kPruneCount], a.counters[7] = a.pruned[kPruneWhole - kPruneCount];
     }
     const uint32_t e0 = tid * kSelectPer;
     if (e0 < a.n) {
@@ -976,7 +976,7 @@ __global__ void __launch_bounds__(256) filter_onepass(const FilterArgs a0) {
         if (threadIdx.x == 0 && a.pruned) {
             a.counters[4] = *a.pruned;
             a.counters[5] = a.pruned[kPruneInplace - kPruneCount];
-            a.counters[6] = a.pruned[kPruneFirst - kPruneCount];
+            a.counters[6] = a.pruned[kPruneFirst - kPruneCount], a.counters[7] = a.pruned[kPruneWhole - kPruneCount];
         }
     }
 #pragma unroll
@@ -1055,8 +1055,13 @@ __global__ void __launch_bounds__(256) pair_tables_kernel(const TableArgs a) {
                          : t == kPruneRem || t == kPruneRem + 1 ? a.prune_rem[t - kPruneRem]
                          : t == kPruneProm || t == kPruneProm + 1 ? a.prune_prom[t - kPruneProm]
                          : t == kPruneCut || t == kPruneCut + 1 ? a.prune_cut[t - kPruneCut]
-                                                                : 0u;
+                         : t == kPruneLen ? a.prune_len
+                         : t == kPruneOrd ? a.prune_ord
+                                          : 0u;
     }
+    if (a.prune_blk && a.prune_len && blockIdx.x == 0)
+        for (uint32_t i = threadIdx.x; i < a.prune_len_n; i += 256)
+            a.prune_blk[kPruneWords + a.prune_len + i] = a.prune_lenmax[i];
     if (a.gate && blockIdx.x == 0 && threadIdx.x == 0) {
         // the long entries' workgroups (another stream) start first; bounded
         // at ~20 ms of the 100 MHz real-time counter, so a gate that is never

@@ -234,9 +234,53 @@ pair_kernel(const StripArgs a) {
         // (through the table's first LDS dword: the first strip's staging
         // starts behind a barrier, after every wave has read it; a static
         // __shared__ word would not fit beside a 160 KiB table)
-        if (threadIdx.x == 0) lds[0] = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0) {
+            uint32_t t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            uint32_t whole = 0;
+            if constexpr (!NW) if (a.nparts > 1 && t < a.nquads) {
+                // (the arguments anew: nothing here may stay in a scalar register across the strips)
+                strip_kargs* const ka = kernargs_again();
+                // a pruned search's part-0 unit (kernels.h kPrune*; one query):
+                // its quad by the host's start order, and the whole unit
+                // skipped when tau is already above what its longest entry can
+                // score at all (lenmax, monotone: the first group's ncols - 1
+                // stands for the longest entry); entries past nmax16 are
+                // never decided here
+                const uint32_t* const pr = ka->part_done - kPruneWords;
+                if (pr[kPruneK] != 0) {
+                    const uint32_t ord = pr[kPruneOrd], lo = pr[kPruneLen];
+                    if (ord) t = ka->part_done[ord + t];
+                    if (lo) {
+                        const uint32_t L = ka->groups[ka->g_first + t * pair_waves(NP, NW)].ncols - 1;
+                        const uint32_t tau = __hip_atomic_load(pr + kPruneTau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        whole = tau != 0 && L <= ka->nmax16 && ka->part_done[lo + min(L, ka->m)] < tau ? 1u : 0u;
+                    }
+                }
+            }
+            lds[0] = t;
+            if constexpr (!NW) lds[2] = whole;      // (not lds[1]: a later part's thread 0 may already be writing its own there)
+        }
         __syncthreads();
         wg = __builtin_amdgcn_readfirstlane(lds[0]);
+        if constexpr (!NW) if (__builtin_amdgcn_readfirstlane(lds[2])) {
+            // every real lane scores plain 0, a lower bound below tau (not
+            // sw_emit's "undecided" 0: nothing is re-scored); the quad's later
+            // units are told to return without emitting, as for a unit that
+            // finished in place: the sentinel, then the flag
+            strip_kargs* const ka = kernargs_again();
+            if (threadIdx.x == 0) {
+                atomicAdd(ka->part_done - kPruneWords + kPruneWhole, 1u);
+                __hip_atomic_store(ka->part_done + 2 * (size_t)wg + 1, kBoundInplace, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __builtin_amdgcn_s_waitcnt(0);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __hip_atomic_store(ka->part_done + 2 * (size_t)wg, ka->part_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            const uint32_t g = ka->g_first + wg * pair_waves(NP, NW) + (threadIdx.x >> 6);
+            if (g >= ka->ngroups) return;
+            const uint32_t o = ka->lane_out[g * 64 + (threadIdx.x & 63)];
+            if (o != 0xffffffffu) ka->scores[o] = 0;
+            return;
+        }
     }
     // several queries (StripArgs::nq): unit = (part, quad, query), query innermost
     const uint32_t nqs = a.nq > 1 ? a.nq : 1u;
