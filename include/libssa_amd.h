@@ -473,11 +473,47 @@ int ssa_amd_score_pairs_indexed( int algo,
  * reverse (the begin cell), directions, walk; NW the last two -- with the
  * direction bits kept in device memory: a chunk holds at most 1 GiB, of which
  * they are the largest part (ssa_amd_align_pairs_stats_t::dir_bytes).
- * Options "pairs_chunk" and "pairs_host" apply as for ssa_amd_score_pairs. */
+ * Options "pairs_chunk" and "pairs_host" apply as for ssa_amd_score_pairs, and
+ *   "pairs_wave" 0|1     1 (default 0): the pairs that qualify (the conditions above; the direction
+ *                        bits counted in the wave kernels' layout) are aligned one WAVE per pair by
+ *                        the kernels of ssa_amd_align_hits below instead of one pair per lane: the
+ *                        same results; a call's device time is then its longest pair's alone, which
+ *                        suits a few long pairs and wastes the chip on many short ones.  The
+ *                        statistics read kernels "wave_fwd,wave_rev,wave_dir,wave_walk" (NW:
+ *                        "wave_dir,wave_walk"), groups = device pairs, launches = chunks x 4
+ *                        (NW: x 2); "pairs_chunk" does not apply (a chunk is 1 GiB of device memory) */
 int ssa_amd_align_pairs( int algo, const uint8_t * q_codes, const uint64_t * q_off,
                          const uint8_t * d_codes, const uint64_t * d_off, size_t npairs,
                          ssa_amd_pair_alignment_t * out, char * cigars, size_t cigar_cap );
 void ssa_amd_get_align_pairs_stats( ssa_amd_align_pairs_stats_t * out );
+/* The alignment list sw_align / nw_align with COMPUTE_ALIGNMENT would return
+ * for exactly these n hits of the open DB (hits as ssa_amd_search and
+ * ssa_amd_search_batch write them: global DB ID, query view, DB strand and
+ * frame; algo SSA_AMD_SW or SSA_AMD_NW), field by field -- the DB sequence
+ * re-fetched as mapped codes, the query borrowed from `query`, the reference's
+ * swap of db_seq.strand and db_seq.frame, score = hits[i].score, region and
+ * CIGAR.  Free it with free_alignment.  Returns NULL, with nothing launched,
+ * for a NULL query, an unknown algo, NULL hits with n > 0, a db_id outside the
+ * open DB's ID range, a query_id that is not one of the query's views or a
+ * strand / frame no entry has.
+ * Both this call and sw_align / nw_align with COMPUTE_ALIGNMENT align their
+ * hits on the device of the search's first slot, one wave per hit
+ * (align_wave.hip: the hit's query rows spread over the lanes, its columns
+ * swept through them; SW forward, SW reverse, directions, walk -- NW the last
+ * two -- enqueued back to back, one upload, one copy back), under
+ * ssa_amd_align_pairs' conditions per hit; every other hit, and every hit when
+ * no gfx950 device is visible, goes through ssa_amd_align_pair's routine on the
+ * host threads (set_thread_count).  The results are identical either way.
+ * ssa_amd_get_align_hits_stats reports the last such alignment stage in
+ * ssa_amd_align_pairs' struct: pairs = hits, total_ms = the whole stage, groups
+ * = hits aligned on the device, device = -1 when nothing was launched;
+ * ssa_amd_get_stats is untouched.  Options:
+ *   "align_wave" 1|0     1 (default): as above; 0: every hit on the host threads, one hit per thread
+ *   "align_wave_min" N   hit lists shorter than N stay on the host (default 1)
+ *   "align_wave_rl" N    query rows per lane of the wave kernels: 0 (default) chosen per call for the
+ *                        fewest row steps, or one of 1 .. 10, 12, 16 (a testing aid; also under "pairs_wave") */
+p_alignment_list ssa_amd_align_hits( p_query query, int algo, const ssa_hit_t * hits, size_t n );
+void ssa_amd_get_align_hits_stats( ssa_amd_align_pairs_stats_t * out );
 /* ASCII -> DB-side residue codes of the current symbol type (us_map_sequence:
  * unknown -> 0); writes min(len, cap) codes, returns len. */
 size_t ssa_amd_map_residues( const char * ascii, size_t len, char * out, size_t cap );

@@ -119,7 +119,8 @@ EXPORTS = {
                       "ssa_amd_score_pairs_ends", "ssa_amd_align_pairs_ends",
                       "ssa_amd_score_pairs_banded", "ssa_amd_align_pairs_banded",
                       "ssa_amd_score_pairs_local", "ssa_amd_align_pairs_local", "ssa_amd_score_pairs_indexed",
-                      "ssa_amd_prune_start_order", "ssa_amd_get_pruned_whole"],
+                      "ssa_amd_prune_start_order", "ssa_amd_get_pruned_whole", "ssa_amd_align_hits",
+                      "ssa_amd_get_align_hits_stats"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -179,6 +180,8 @@ def load():
         "ssa_amd_align_pairs": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                                  c_size_t], c_int),
         "ssa_amd_get_align_pairs_stats": ([POINTER(ssa_amd_align_pairs_stats_t)], None),
+        "ssa_amd_align_hits": ([P, c_int, POINTER(ssa_hit_t), c_size_t], POINTER(alignment_list_t)),
+        "ssa_amd_get_align_hits_stats": ([POINTER(ssa_amd_align_pairs_stats_t)], None),
         "ssa_amd_score_pairs_ends": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
         "ssa_amd_align_pairs_ends": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                                       c_size_t], c_int),
@@ -715,6 +718,30 @@ def align_pairs_stats():
     """ssa_amd_get_align_pairs_stats: the last align_pairs call as a dict."""
     s = ssa_amd_align_pairs_stats_t()
     load().ssa_amd_get_align_pairs_stats(ctypes.byref(s))
+    d = {f: getattr(s, f) for f, _ in ssa_amd_align_pairs_stats_t._fields_}
+    d["kernels"] = d["kernels"].decode()
+    return d
+
+
+def align_hits(q, algo, hits):
+    """ssa_amd_align_hits: the alignment list (dicts, as sw_align returns them)
+    sw_align / nw_align with COMPUTE_ALIGNMENT would give for these hits of the
+    open DB -- tuples (score, db_id[, query_id, db_strand, db_frame]) as search
+    and search_batch return them.  None when the library refuses the hits."""
+    L = load()
+    al = L.ssa_amd_align_hits(q, algo, _hit_array(hits), len(hits))
+    if not al:
+        return None
+    res = _unpack(al)
+    L.free_alignment(al)
+    return res
+
+
+def align_hits_stats():
+    """ssa_amd_get_align_hits_stats: the last COMPUTE_ALIGNMENT / align_hits
+    alignment stage as a dict (align_pairs_stats' fields)."""
+    s = ssa_amd_align_pairs_stats_t()
+    load().ssa_amd_get_align_hits_stats(ctypes.byref(s))
     d = {f: getattr(s, f) for f, _ in ssa_amd_align_pairs_stats_t._fields_}
     d["kernels"] = d["kernels"].decode()
     return d

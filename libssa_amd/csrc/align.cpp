@@ -197,8 +197,12 @@ std::string traceback(int algo, const uint8_t* q, size_t qn, const uint8_t* d, s
     return cigar(dir, qn, rg);
 }
 
-// Fills region and CIGAR of every alignment in the list, in parallel.
-void compute_alignments(p_alignment_list L, int algo) {
+// Fills region and CIGAR of every alignment in the list: on the wave kernels
+// (align_wave.cpp), or on the host below.
+void compute_alignments(p_alignment_list L, int algo) { align_hits(L, algo); }
+
+// Fills region and CIGAR of every alignment in the list, in parallel on the host.
+void compute_alignments_host(p_alignment_list L, int algo) {
     const size_t n = L->len;
     if (n == 0) return;
     size_t workers = std::max<size_t>(1, std::min<size_t>(n, std::thread::hardware_concurrency()));

@@ -679,6 +679,28 @@ void ssa_amd_get_align_pairs_stats(ssa_amd_align_pairs_stats_t* out) {
     if (out) *out = align_pairs_stats();
 }
 
+void ssa_amd_get_align_hits_stats(ssa_amd_align_pairs_stats_t* out) {
+    if (out) *out = align_hits_stats();
+}
+
+p_alignment_list ssa_amd_align_hits(p_query query, int algo, const ssa_hit_t* hits, size_t n) {
+    if (!query || (algo != SSA_AMD_SW && algo != SSA_AMD_NW) || (n > 0 && !hits)) return nullptr;
+    test_configuration(query);
+    SearchResult R;
+    R.views = query_views(query);
+    const uint64_t first = cfg().id_offset, count = ssa_db_get_sequence_count();
+    for (size_t i = 0; i < n; i++) {
+        const ssa_hit_t& h = hits[i];
+        if (h.db_id < first || h.db_id - first >= count || h.query_id >= R.views.size() || h.db_strand > 1 ||
+            h.db_frame > 2)
+            return nullptr;
+        R.hits.push_back(Hit{h.score, h.db_id, h.query_id, h.db_strand, h.db_frame});
+    }
+    p_alignment_list L = build_list(R);
+    compute_alignments(L, algo == SSA_AMD_NW ? kAlgoNW : kAlgoSW);
+    return L;
+}
+
 int ssa_amd_score_pairs_ends(int ends, const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes,
                              const uint64_t* d_off, size_t npairs, int64_t* scores) {
     return score_pairs_ends(ends, q_codes, q_off, d_codes, d_off, npairs, scores);
@@ -783,6 +805,10 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "pairs_host")) cfg().pairs_host = (int)value;
     else if (!strcmp(name, "pairs_gather")) cfg().pairs_gather = (int)value;
     else if (!strcmp(name, "pairs_pool_mb")) cfg().pairs_pool_mb = (int)std::max(0L, std::min(value, 1L << 20));
+    else if (!strcmp(name, "pairs_wave")) cfg().pairs_wave = (int)value;
+    else if (!strcmp(name, "align_wave")) cfg().align_wave = (int)value;
+    else if (!strcmp(name, "align_wave_min")) cfg().align_wave_min = (int)std::max(0L, std::min(value, 1L << 30));
+    else if (!strcmp(name, "align_wave_rl")) cfg().align_wave_rl = (int)value;
     else if (!strcmp(name, "filter_prefix_regs")) set_filter_prefix_regs((int)value);
     else print_warning("unknown option %s", name);
 }

@@ -86,6 +86,12 @@ struct Config {
     int pairs_gather = 1;                 // ssa_amd_score_pairs_indexed: 1 (default) packs on the device from the
                                           // uploaded pools (pairs_gather.hip), 0 packs on the host
     int pairs_pool_mb = 1024;             // ... and packs on the host when the pools exceed this many MiB
+    int pairs_wave = 0;                   // 1: ssa_amd_align_pairs aligns on the wave kernels, one wave per pair
+                                          // (align_wave.cpp); 0: one pair per lane (pairs_align.cpp)
+    int align_wave = 1;                   // COMPUTE_ALIGNMENT and ssa_amd_align_hits on the wave kernels; 0: host threads
+    int align_wave_min = 1;               // ... for hit lists of at least this many hits
+    int align_wave_rl = 0;                // the wave kernels' rows per lane: 0 by cost (align_wave.cpp pick_rl),
+                                          // else one of align_wave.h's kWaveRL forced
     int topk_prune = 1;                   // SW top-k searches on the pair kernel skip the strip parts of groups
                                           // that can no longer reach the top-k (StripArgs::prune)
     int prune_inplace_pct = 25;           // a pruned search's work unit that cannot be skipped at a part boundary
@@ -199,6 +205,21 @@ void sort_hits(std::vector<Hit>& v);   // score desc, id desc (util.h:12)
 // align.cpp: region {q begin, q end, db begin, db end} and CIGAR of a pair
 std::string traceback(int algo, const uint8_t* q, size_t qn, const uint8_t* d, size_t dn, size_t region[4]);
 void compute_alignments(p_alignment_list L, int algo);
+void compute_alignments_host(p_alignment_list L, int algo);   // ... on host threads, one hit per thread
+// align_wave.cpp: the wave aligner (one wave per pair on the device).  Region, CIGAR length, flags (and the
+// score when asked for) of every item go to out[i], the NUL-terminated text to items[i].text (qlen + dlen + 1
+// bytes); device < 0: ssa_amd_set_device's, else the current one
+struct WaveItem {
+    const uint8_t* q;
+    size_t qlen;
+    const uint8_t* d;
+    size_t dlen;
+    char* text;
+};
+void align_wave(int algo, const WaveItem* items, size_t n, int device, bool allow_device, bool want_score,
+                ssa_amd_pair_alignment_t* out, ssa_amd_align_pairs_stats_t& stats);
+void align_hits(p_alignment_list L, int algo);                // compute_alignments' body
+const ssa_amd_align_pairs_stats_t& align_hits_stats();
 
 // ------------------------------------------------------------ pair batches
 // pairs.cpp: ssa_amd_score_pairs and its statistics

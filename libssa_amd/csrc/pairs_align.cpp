@@ -93,6 +93,19 @@ int align_pairs(int algo, const uint8_t* qc, const uint64_t* qoff, const uint8_t
     for (size_t i = 0; i < n; i++) coff[i + 1] = coff[i] + (qoff[i + 1] - qoff[i]) + (doff[i + 1] - doff[i]) + 1;
     if (cigar_cap < coff[n]) return 1;
 
+    if (cfg().pairs_wave) {
+        // option "pairs_wave": one wave per pair (align_wave.cpp) instead of one pair per lane
+        std::vector<WaveItem> items(n);
+        for (size_t i = 0; i < n; i++) {
+            items[i] = WaveItem{qc + qoff[i], (size_t)(qoff[i + 1] - qoff[i]), dc + doff[i],
+                                (size_t)(doff[i + 1] - doff[i]), cigars + coff[i]};
+            out[i].cigar_off = coff[i];
+        }
+        align_wave(nw ? kAlgoNW : kAlgoSW, items.data(), n, -1, !cfg().pairs_host, true, out, g_stats);
+        g_stats.total_ms = now_ms() - t0;
+        return 0;
+    }
+
     const Config& C = cfg();
     const int64_t* M = matrix().m;
     const int64_t Q = C.gap_open, Ge = C.gap_extend;
