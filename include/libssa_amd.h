@@ -706,6 +706,55 @@ int ssa_amd_align_pairs_local( int mode, const int64_t * band_lo, const int64_t 
                                const uint8_t * d_codes, const uint64_t * d_off, size_t npairs,
                                ssa_amd_pair_alignment_t * out, char * cigars, size_t cigar_cap );
 
+/* What a batch caller thresholds on -- identity, aligned columns and the region
+ * for coverage -- without the traceback: one pair's result of
+ * ssa_amd_summarize_pairs_local. */
+typedef struct {
+    int64_t  score;       /* ssa_amd_score_pairs_local's */
+    uint64_t region[4];   /* q begin, q end, d begin, d end -- ssa_amd_align_pairs_local's */
+    uint32_t columns;     /* operations of that call's CIGAR: M + I + D */
+    uint32_t matched;     /* its M columns */
+    uint32_t identical;   /* M columns whose q code equals the d code (mapped codes compared) */
+    uint32_t flags;       /* bit 0: summarized on the host path */
+} ssa_amd_pair_summary_t;   /* 56 bytes */
+
+/* Pair i's score and region are exactly what ssa_amd_align_pairs_local returns
+ * with the same mode, bands, sequences, matrix and penalties; columns and
+ * matched count that call's CIGAR, and identical counts the M columns in which
+ * the two residue codes are equal when the text is walked from (q begin, d
+ * begin).  All 64 modes are accepted, through their 25 canonical ones; NULL
+ * bands mean unbanded; modes below 16 are the ends-free and banded
+ * definitions.  Where that call has no CIGAR -- an empty side, a zero score
+ * under a local bit -- every counter and the region are 0.  A leading D or I
+ * run of a begin that is not free counts in columns, as it does in the text;
+ * columns = (q end - q begin + 1) + (d end - d begin + 1) - matched always.
+ * Arguments, checks, band validity, return codes and "nothing written, nothing
+ * launched" are ssa_amd_score_pairs_local's, and out == NULL with npairs > 0
+ * returns non-zero; there is no CIGAR buffer.  Options "pairs_chunk" and
+ * "pairs_host" apply.
+ * Nothing of the traceback is kept: a chunk (256 MiB of residues and row
+ * buffers) runs the score pass, which leaves the end cell, and one sweep that
+ * carries, beside every H, E and F, the counters and the begin of the path the
+ * walk would take from it, selected by the comparisons that define the
+ * direction bits; the words at the end cell are the result, ties included.  No
+ * direction bits, walk, runs or text exist on the device path.
+ * Device conditions: ssa_amd_score_pairs_local's (a device visible, the matrix
+ * in int8, gap penalties <= 0, (qlen + dlen) inside the 2^29 score bound, two
+ * non-empty sides) and both lengths below 65 535, because positions travel as
+ * 16 + 16 bits.  No direction-bit budget applies: a 60 000 x 60 000 unbanded
+ * pair is a device pair.  Every other pair takes the host path -- the host
+ * align routine of the canonical mode, its text counted in place, quadratic
+ * memory in the band -- and has bit 0 of flags set.
+ * Statistics through ssa_amd_get_align_pairs_stats: pairs, cells, host_pairs,
+ * zero_pairs, groups, chunks; launches = 2 * chunks; kernels =
+ * "pairs_summary_end,pairs_summary_sweep" (empty when nothing was launched);
+ * fwd_ms = the end-cell pass, dir_ms = the summary sweep, rev_ms = walk_ms =
+ * text_ms = 0, kernel_ms their sum; dir_bytes = 0; device_fallbacks = 0. */
+int ssa_amd_summarize_pairs_local( int mode, const int64_t * band_lo, const int64_t * band_hi,
+                                   const uint8_t * q_codes, const uint64_t * q_off,
+                                   const uint8_t * d_codes, const uint64_t * d_off,
+                                   size_t npairs, ssa_amd_pair_summary_t * out );
+
 #ifdef __cplusplus
 }
 #endif

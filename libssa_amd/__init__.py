@@ -89,6 +89,11 @@ class ssa_amd_pair_alignment_t(Structure):
                 ("flags", c_uint32)]
 
 
+class ssa_amd_pair_summary_t(Structure):
+    _fields_ = [("score", c_int64), ("region", c_uint64 * 4), ("columns", c_uint32), ("matched", c_uint32),
+                ("identical", c_uint32), ("flags", c_uint32)]
+
+
 class ssa_amd_align_pairs_stats_t(Structure):
     _fields_ = [("pairs", c_uint64), ("cells", c_uint64), ("host_pairs", c_uint64), ("zero_pairs", c_uint64),
                 ("device_fallbacks", c_uint64), ("dir_bytes", c_uint64), ("groups", c_uint32), ("chunks", c_uint32),
@@ -101,6 +106,7 @@ class ssa_amd_align_pairs_stats_t(Structure):
 assert ctypes.sizeof(db_seq_t) == 32 and ctypes.sizeof(q_seq_t) == 24
 assert ctypes.sizeof(alignment_t) == 112 and ctypes.sizeof(alignment_list_t) == 16
 assert ctypes.sizeof(ssa_hit_t) == 24 and ctypes.sizeof(ssa_amd_pair_alignment_t) == 56
+assert ctypes.sizeof(ssa_amd_pair_summary_t) == 56
 
 # every symbol include/*.h declares (checked by tests/test_abi.py)
 EXPORTS = {
@@ -120,7 +126,7 @@ EXPORTS = {
                       "ssa_amd_score_pairs_banded", "ssa_amd_align_pairs_banded",
                       "ssa_amd_score_pairs_local", "ssa_amd_align_pairs_local", "ssa_amd_score_pairs_indexed",
                       "ssa_amd_prune_start_order", "ssa_amd_get_pruned_whole", "ssa_amd_align_hits",
-                      "ssa_amd_get_align_hits_stats"],
+                      "ssa_amd_get_align_hits_stats", "ssa_amd_summarize_pairs_local"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -193,6 +199,8 @@ def load():
                                        c_void_p], c_int),
         "ssa_amd_align_pairs_local": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                        c_void_p, c_void_p, c_size_t], c_int),
+        "ssa_amd_summarize_pairs_local": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p], c_int),
         "ssa_amd_map_residues": ([c_char_p, c_size_t, c_char_p, c_size_t], c_size_t),
         "ssa_amd_shard_bounds": ([c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_size_t)], c_int),
     }
@@ -712,6 +720,45 @@ def align_pairs_local_flat(mode, q_codes, q_off, d_codes, d_off, band_lo=None, b
     """ssa_amd_align_pairs_local on the C layout itself: (out, cigars) as align_pairs_flat."""
     return _align_flat("ssa_amd_align_pairs_local", "align_pairs_local_flat", mode, q_codes, q_off, d_codes, d_off,
                        band=(band_lo, band_hi))
+
+
+SUMMARY_DTYPE = [("score", "<i8"), ("region", "<u8", (4,)), ("columns", "<u4"), ("matched", "<u4"),
+                 ("identical", "<u4"), ("flags", "<u4")]
+
+
+def summarize_pairs_local(mode, queries, targets, band_lo=None, band_hi=None):
+    """ssa_amd_summarize_pairs_local: [(score, (q_begin, q_end, d_begin,
+    d_end), columns, matched, identical, flags)] of align_pairs_local's
+    alignments, without their CIGARs; a pair that has none there is all zeros
+    behind its score.  Shapes and errors as align_pairs_local."""
+    if len(queries) != len(targets):
+        raise ValueError("summarize_pairs_local: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    out = summarize_pairs_local_flat(mode, q, qo, d, do, band_lo, band_hi)
+    return [(int(o["score"]), tuple(int(x) for x in o["region"]), int(o["columns"]), int(o["matched"]),
+             int(o["identical"]), int(o["flags"])) for o in out]
+
+
+def summarize_pairs_local_flat(mode, q_codes, q_off, d_codes, d_off, band_lo=None, band_hi=None):
+    """ssa_amd_summarize_pairs_local on the C layout itself (score_pairs_banded_flat's
+    arrays): a structured array of ssa_amd_pair_summary_t records (SUMMARY_DTYPE)."""
+    import numpy as np
+    name, symbol = "summarize_pairs_local_flat", "ssa_amd_summarize_pairs_local"
+    for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
+        if a.dtype != t or not a.flags.c_contiguous:
+            raise ValueError(f"{name}: contiguous uint8 codes and uint64 offsets expected")
+    if len(q_off) != len(d_off) or len(q_off) < 1:
+        raise ValueError(f"{name}: offset arrays of npairs + 1 entries expected")
+    n = len(q_off) - 1
+    out = np.zeros(n, np.dtype(SUMMARY_DTYPE))
+    assert out.dtype.itemsize == ctypes.sizeof(ssa_amd_pair_summary_t)
+    band = _band_arrays(name, (band_lo, band_hi), n)
+    rc = getattr(load(), symbol)(mode, *(None if b is None else b.ctypes.data for b in band), q_codes.ctypes.data,
+                                 q_off.ctypes.data, d_codes.ctypes.data, d_off.ctypes.data, n, out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"{symbol} refused its arguments ({rc})")
+    return out
 
 
 def align_pairs_stats():

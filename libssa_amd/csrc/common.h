@@ -255,6 +255,10 @@ int score_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_hi, 
 int align_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* q_codes,
                       const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off, size_t npairs,
                       ssa_amd_pair_alignment_t* out, char* cigars, size_t cigar_cap);
+// pairs_summary.cpp: ssa_amd_summarize_pairs_local; it reports through the align statistics
+int summarize_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* q_codes,
+                          const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off, size_t npairs,
+                          ssa_amd_pair_summary_t* out);
 void set_pairs_stats(const ssa_amd_pairs_stats_t& s);
 void set_align_pairs_stats(const ssa_amd_align_pairs_stats_t& s);
 

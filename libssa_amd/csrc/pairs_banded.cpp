@@ -409,6 +409,12 @@ BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const
     return K;
 }
 
+void banded_host_align(int ends, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,
+                       ssa_amd_pair_alignment_t& o, char* text) {
+    HostScratch S;
+    host_align(ends, q, ql, d, dl, lo, hi, S, o, text);
+}
+
 double banded_elapsed(int e) {
     float ms = 0;
     check(hipEventElapsedTime(&ms, g_dev.ev[e], g_dev.ev[e + 1]), "hipEventElapsedTime");

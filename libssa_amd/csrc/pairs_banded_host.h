@@ -1,5 +1,5 @@
 // pairs_banded_host.h -- the host side of the banded pair calls that the local
-// pair calls share (defined in pairs_banded.cpp; used by pairs_local.cpp): the
+// pair calls share (defined in pairs_banded.cpp; used by pairs_local.cpp and pairs_summary.cpp): the
 // band's clamp and validity rule, the batch ordered by shape and band with its
 // BandStrip ranges, the chunk packer and the device buffers it fills.  Host
 // code only.
@@ -73,5 +73,19 @@ struct BandChunk {
 // group), packs it lane-interleaved into the pinned block and enqueues its
 // upload; sizes every device buffer banded_kernel and banded_walk_kernel touch.
 BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const EndsRouting& T);
+
+// ------------------------------------ what the summary call shares (pairs_summary.cpp)
+// One pair through the host align routine of the banded calls (pairs_banded.cpp; ends: the mask) or of the
+// local calls (pairs_local.cpp; mode: canonical, with a local bit), a clamped valid band, scratch of the
+// call's own; text: qlen + dlen + 1 bytes.  local_host_align returns true for the empty alignment of two
+// non-empty sides.
+void banded_host_align(int ends, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,
+                       ssa_amd_pair_alignment_t& o, char* text);
+bool local_host_align(int mode, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,
+                      ssa_amd_pair_alignment_t& o, char* text);
+// the local calls' canonical mode, and their band check (NULL bands: the full range of every pair)
+int local_canonical(int mode);
+bool local_bands_ok(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint64_t* qoff,
+                    const uint64_t* doff, size_t n, std::vector<int64_t>& lo, std::vector<int64_t>& hi);
 
 }  // namespace ssa

@@ -241,6 +241,20 @@ LocalArgs local_args(const BandChunk& K, int mode, bool align) {
 
 }  // namespace
 
+// ---- shared with pairs_summary.cpp (pairs_banded_host.h)
+int local_canonical(int mode) { return canonical(mode); }
+
+bool local_bands_ok(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint64_t* qoff,
+                    const uint64_t* doff, size_t n, std::vector<int64_t>& lo, std::vector<int64_t>& hi) {
+    return bands_ok(mode, band_lo, band_hi, qoff, doff, n, lo, hi);
+}
+
+bool local_host_align(int mode, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,
+                      ssa_amd_pair_alignment_t& o, char* text) {
+    HostScratch S;
+    return host_align(mode, q, ql, d, dl, lo, hi, S, o, text);
+}
+
 int score_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* qc,
                       const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff, size_t n, int64_t* scores) {
     const double t0 = now_ms();
