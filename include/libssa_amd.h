@@ -755,6 +755,68 @@ int ssa_amd_summarize_pairs_local( int mode, const int64_t * band_lo, const int6
                                    const uint8_t * d_codes, const uint64_t * d_off,
                                    size_t npairs, ssa_amd_pair_summary_t * out );
 
+/* X-drop extension: the local calls of a mode with LOCAL_END and without
+ * LOCAL_BEGIN, whose alignment stops once a whole row has fallen more than
+ * `xdrop` below the best score seen (the rule of BLAST's gapped extension and
+ * of ksw2's Z-drop, without the latter's diagonal term).  xdrop is >= 0; `mode`
+ * must canonicalise to 42, 43, 46 or 47.  Everything not said here is
+ * ssa_amd_*_pairs_local's and stays as it is: bands, boundary cells, the
+ * recurrence, "a cell exists", minus infinity, the walk, the CIGAR contract,
+ * empty sides, band validity and NULL bands.  No cell is pruned -- every H, E,
+ * F and direction bit is the local call's -- only the set of end candidates is
+ * cut, row by row.  For row i (0 <= i < qlen) let C_i be the existing real
+ * cells (i, j) with a finite H, m_i the greatest H in C_i and c_i the smallest
+ * column that attains m_i.  Walk the rows in ascending order, starting with
+ * best = 0 and no end cell:
+ *   - C_i empty (no cell of the row in the band or in the matrix, or none
+ *     reachable): the row is passed over;
+ *   - else best - m_i > xdrop: stop.  Row i is the DROP ROW; rows >= i hold no
+ *     candidate;
+ *   - else m_i > best: the end cell becomes (i, c_i) and best = m_i; the same
+ *     if m_i == best, an end cell exists and c_i is smaller than its column.
+ * The score is best; 0 means the empty alignment (region zeros, empty CIGAR,
+ * counted in zero_pairs).  Equivalently the result is the local call's with
+ * its candidates restricted to the rows before the drop row; ties keep the
+ * local rule, the smallest (d_end, q_end).  An xdrop at or above 2^30 never
+ * stops a device pair (the host clamps it; device scores lie inside 2^29), so
+ * the result is then exactly the local call's.  Not part of this: ksw2's
+ * diagonal term, per-pair drops, LOCAL_BEGIN modes (a left extension is the
+ * right extension of the reversed sequences), pruning of columns.
+ * Arguments, checks, return codes, "nothing written, nothing launched",
+ * options ("pairs_chunk", "pairs_host"), device conditions, host routing and
+ * the statistics getters are the corresponding local calls'; a negative xdrop
+ * and a mode whose canonical form is not 42, 43, 46 or 47 also return
+ * non-zero.  The host path is the local calls' int64 routine with the row rule
+ * (its loop stops at the drop row; flags bit 0).  On the device a chunk first
+ * runs the end pass, the local score pass with the candidates tracked per row;
+ * a wave leaves its strip loop once every lane has met its drop row or run out
+ * of rows.
+ * ssa_amd_score_pairs_xdrop reports kernel "pairs_xdrop_i32"; swept_cells
+ * counts only the column blocks of the strips the waves entered.
+ * ssa_amd_align_pairs_xdrop reports kernels
+ * "pairs_xdrop_end,pairs_local_dir,pairs_local_walk", fwd_ms = the end pass:
+ * after it every group is cut to the strip of its furthest end row (a group
+ * without an end cell to nothing), and the local direction pass and walk run
+ * on what is left; dir_bytes counts the direction bits that were swept.  The
+ * 512 MiB condition of a pair is the local align call's, planned for the whole
+ * band.  ssa_amd_summarize_pairs_xdrop reports kernels
+ * "pairs_xdrop_end,pairs_summary_sweep", with the same cut.
+ * ssa_amd_get_xdrop_dropped: the pairs of the last xdrop call that met a drop
+ * row, device and host pairs alike. */
+int ssa_amd_score_pairs_xdrop( int mode, int64_t xdrop, const int64_t * band_lo, const int64_t * band_hi,
+                               const uint8_t * q_codes, const uint64_t * q_off,
+                               const uint8_t * d_codes, const uint64_t * d_off,
+                               size_t npairs, int64_t * scores );
+int ssa_amd_align_pairs_xdrop( int mode, int64_t xdrop, const int64_t * band_lo, const int64_t * band_hi,
+                               const uint8_t * q_codes, const uint64_t * q_off,
+                               const uint8_t * d_codes, const uint64_t * d_off, size_t npairs,
+                               ssa_amd_pair_alignment_t * out, char * cigars, size_t cigar_cap );
+int ssa_amd_summarize_pairs_xdrop( int mode, int64_t xdrop, const int64_t * band_lo, const int64_t * band_hi,
+                                   const uint8_t * q_codes, const uint64_t * q_off,
+                                   const uint8_t * d_codes, const uint64_t * d_off,
+                                   size_t npairs, ssa_amd_pair_summary_t * out );
+uint64_t ssa_amd_get_xdrop_dropped( void );
+
 #ifdef __cplusplus
 }
 #endif

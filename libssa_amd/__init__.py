@@ -126,7 +126,9 @@ EXPORTS = {
                       "ssa_amd_score_pairs_banded", "ssa_amd_align_pairs_banded",
                       "ssa_amd_score_pairs_local", "ssa_amd_align_pairs_local", "ssa_amd_score_pairs_indexed",
                       "ssa_amd_prune_start_order", "ssa_amd_get_pruned_whole", "ssa_amd_align_hits",
-                      "ssa_amd_get_align_hits_stats", "ssa_amd_summarize_pairs_local"],
+                      "ssa_amd_get_align_hits_stats", "ssa_amd_summarize_pairs_local",
+                      "ssa_amd_score_pairs_xdrop", "ssa_amd_align_pairs_xdrop", "ssa_amd_summarize_pairs_xdrop",
+                      "ssa_amd_get_xdrop_dropped"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -201,6 +203,13 @@ def load():
                                        c_void_p, c_void_p, c_size_t], c_int),
         "ssa_amd_summarize_pairs_local": ([c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_size_t, c_void_p], c_int),
+        "ssa_amd_score_pairs_xdrop": ([c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p], c_int),
+        "ssa_amd_align_pairs_xdrop": ([c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p, c_void_p, c_size_t], c_int),
+        "ssa_amd_summarize_pairs_xdrop": ([c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p], c_int),
+        "ssa_amd_get_xdrop_dropped": ([], c_uint64),
         "ssa_amd_map_residues": ([c_char_p, c_size_t, c_char_p, c_size_t], c_size_t),
         "ssa_amd_shard_bounds": ([c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_size_t)], c_int),
     }
@@ -522,7 +531,7 @@ def _band_arrays(name, band, n):
     return lo, hi
 
 
-def _score_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band=None):
+def _score_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band=None, extra=()):
     import numpy as np
     for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
         if a.dtype != t or not a.flags.c_contiguous:
@@ -532,8 +541,9 @@ def _score_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band=None):
     n = len(q_off) - 1
     out = np.zeros(n, np.int64)
     band = _band_arrays(name, band, n)
-    rc = getattr(load(), symbol)(mode, *(None if b is None else b.ctypes.data for b in band), q_codes.ctypes.data, q_off.ctypes.data,
-                                 d_codes.ctypes.data, d_off.ctypes.data, n, out.ctypes.data)
+    rc = getattr(load(), symbol)(mode, *extra, *(None if b is None else b.ctypes.data for b in band),
+                                 q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data, d_off.ctypes.data, n,
+                                 out.ctypes.data)
     if rc != 0:
         raise ValueError(f"{symbol} refused its arguments ({rc})")
     return out
@@ -573,7 +583,7 @@ def align_pairs_flat(algo, q_codes, q_off, d_codes, d_off):
     return _align_flat("ssa_amd_align_pairs", "align_pairs_flat", algo, q_codes, q_off, d_codes, d_off)
 
 
-def _align_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band=None):
+def _align_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band=None, extra=()):
     import numpy as np
     for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
         if a.dtype != t or not a.flags.c_contiguous:
@@ -588,8 +598,9 @@ def _align_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band=None):
         cap = int(q_off[n] - q_off[0]) + int(d_off[n] - d_off[0]) + n
     cigars = np.zeros(cap, np.uint8)
     band = _band_arrays(name, band, n)
-    rc = getattr(load(), symbol)(mode, *(None if b is None else b.ctypes.data for b in band), q_codes.ctypes.data, q_off.ctypes.data,
-                                 d_codes.ctypes.data, d_off.ctypes.data, n, out.ctypes.data, cigars.ctypes.data, cap)
+    rc = getattr(load(), symbol)(mode, *extra, *(None if b is None else b.ctypes.data for b in band),
+                                 q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data, d_off.ctypes.data, n,
+                                 out.ctypes.data, cigars.ctypes.data, cap)
     if rc != 0:
         raise ValueError(f"{symbol} refused its arguments ({rc})")
     return out, cigars
@@ -743,8 +754,12 @@ def summarize_pairs_local(mode, queries, targets, band_lo=None, band_hi=None):
 def summarize_pairs_local_flat(mode, q_codes, q_off, d_codes, d_off, band_lo=None, band_hi=None):
     """ssa_amd_summarize_pairs_local on the C layout itself (score_pairs_banded_flat's
     arrays): a structured array of ssa_amd_pair_summary_t records (SUMMARY_DTYPE)."""
+    return _summary_flat("ssa_amd_summarize_pairs_local", "summarize_pairs_local_flat", mode, q_codes, q_off, d_codes,
+                         d_off, band_lo, band_hi)
+
+
+def _summary_flat(symbol, name, mode, q_codes, q_off, d_codes, d_off, band_lo, band_hi, extra=()):
     import numpy as np
-    name, symbol = "summarize_pairs_local_flat", "ssa_amd_summarize_pairs_local"
     for a, t in ((q_codes, np.uint8), (d_codes, np.uint8), (q_off, np.uint64), (d_off, np.uint64)):
         if a.dtype != t or not a.flags.c_contiguous:
             raise ValueError(f"{name}: contiguous uint8 codes and uint64 offsets expected")
@@ -754,11 +769,76 @@ def summarize_pairs_local_flat(mode, q_codes, q_off, d_codes, d_off, band_lo=Non
     out = np.zeros(n, np.dtype(SUMMARY_DTYPE))
     assert out.dtype.itemsize == ctypes.sizeof(ssa_amd_pair_summary_t)
     band = _band_arrays(name, (band_lo, band_hi), n)
-    rc = getattr(load(), symbol)(mode, *(None if b is None else b.ctypes.data for b in band), q_codes.ctypes.data,
-                                 q_off.ctypes.data, d_codes.ctypes.data, d_off.ctypes.data, n, out.ctypes.data)
+    rc = getattr(load(), symbol)(mode, *extra, *(None if b is None else b.ctypes.data for b in band),
+                                 q_codes.ctypes.data, q_off.ctypes.data, d_codes.ctypes.data, d_off.ctypes.data, n,
+                                 out.ctypes.data)
     if rc != 0:
         raise ValueError(f"{symbol} refused its arguments ({rc})")
     return out
+
+
+def _xdrop_value(name, xdrop):
+    x = int(xdrop)
+    if not -(1 << 63) <= x < (1 << 63):
+        raise ValueError(f"{name}: xdrop outside int64")
+    return x
+
+
+def score_pairs_xdrop(mode, xdrop, queries, targets, band_lo=None, band_hi=None):
+    """ssa_amd_score_pairs_xdrop: score_pairs_local under a mode that
+    canonicalises to 42, 43, 46 or 47, with the end candidates cut at the
+    first row whose greatest H lies more than `xdrop` (>= 0) below the best
+    score so far.  Raises ValueError when the library refuses the arguments."""
+    if len(queries) != len(targets):
+        raise ValueError("score_pairs_xdrop: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    return score_pairs_xdrop_flat(mode, xdrop, q, qo, d, do, band_lo, band_hi)
+
+
+def score_pairs_xdrop_flat(mode, xdrop, q_codes, q_off, d_codes, d_off, band_lo=None, band_hi=None):
+    """ssa_amd_score_pairs_xdrop on the C layout itself (score_pairs_banded_flat's arrays)."""
+    return _score_flat("ssa_amd_score_pairs_xdrop", "score_pairs_xdrop_flat", mode, q_codes, q_off, d_codes, d_off,
+                       band=(band_lo, band_hi), extra=(_xdrop_value("score_pairs_xdrop_flat", xdrop),))
+
+
+def align_pairs_xdrop(mode, xdrop, queries, targets, band_lo=None, band_hi=None):
+    """ssa_amd_align_pairs_xdrop: [(score, (q_begin, q_end, d_begin, d_end),
+    cigar)] of the same alignments; shapes and errors as align_pairs_local."""
+    if len(queries) != len(targets):
+        raise ValueError("align_pairs_xdrop: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    return _alignment_list(*align_pairs_xdrop_flat(mode, xdrop, q, qo, d, do, band_lo, band_hi))
+
+
+def align_pairs_xdrop_flat(mode, xdrop, q_codes, q_off, d_codes, d_off, band_lo=None, band_hi=None):
+    """ssa_amd_align_pairs_xdrop on the C layout itself: (out, cigars) as align_pairs_flat."""
+    return _align_flat("ssa_amd_align_pairs_xdrop", "align_pairs_xdrop_flat", mode, q_codes, q_off, d_codes, d_off,
+                       band=(band_lo, band_hi), extra=(_xdrop_value("align_pairs_xdrop_flat", xdrop),))
+
+
+def summarize_pairs_xdrop(mode, xdrop, queries, targets, band_lo=None, band_hi=None):
+    """ssa_amd_summarize_pairs_xdrop: summarize_pairs_local's tuples of
+    align_pairs_xdrop's alignments, without their CIGARs."""
+    if len(queries) != len(targets):
+        raise ValueError("summarize_pairs_xdrop: queries and targets differ in length")
+    q, qo = _concat_codes(queries)
+    d, do = _concat_codes(targets)
+    out = summarize_pairs_xdrop_flat(mode, xdrop, q, qo, d, do, band_lo, band_hi)
+    return [(int(o["score"]), tuple(int(x) for x in o["region"]), int(o["columns"]), int(o["matched"]),
+             int(o["identical"]), int(o["flags"])) for o in out]
+
+
+def summarize_pairs_xdrop_flat(mode, xdrop, q_codes, q_off, d_codes, d_off, band_lo=None, band_hi=None):
+    """ssa_amd_summarize_pairs_xdrop on the C layout itself: SUMMARY_DTYPE records."""
+    return _summary_flat("ssa_amd_summarize_pairs_xdrop", "summarize_pairs_xdrop_flat", mode, q_codes, q_off, d_codes,
+                         d_off, band_lo, band_hi, extra=(_xdrop_value("summarize_pairs_xdrop_flat", xdrop),))
+
+
+def xdrop_dropped():
+    """ssa_amd_get_xdrop_dropped: pairs of the last xdrop call that met a drop row."""
+    return int(load().ssa_amd_get_xdrop_dropped())
 
 
 def align_pairs_stats():

@@ -742,6 +742,28 @@ int ssa_amd_summarize_pairs_local(int mode, const int64_t* band_lo, const int64_
     return summarize_pairs_local(mode, band_lo, band_hi, q_codes, q_off, d_codes, d_off, npairs, out);
 }
 
+int ssa_amd_score_pairs_xdrop(int mode, int64_t xdrop, const int64_t* band_lo, const int64_t* band_hi,
+                              const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes,
+                              const uint64_t* d_off, size_t npairs, int64_t* scores) {
+    return score_pairs_xdrop(mode, xdrop, band_lo, band_hi, q_codes, q_off, d_codes, d_off, npairs, scores);
+}
+
+int ssa_amd_align_pairs_xdrop(int mode, int64_t xdrop, const int64_t* band_lo, const int64_t* band_hi,
+                              const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes,
+                              const uint64_t* d_off, size_t npairs, ssa_amd_pair_alignment_t* out, char* cigars,
+                              size_t cigar_cap) {
+    return align_pairs_xdrop(mode, xdrop, band_lo, band_hi, q_codes, q_off, d_codes, d_off, npairs, out, cigars,
+                             cigar_cap);
+}
+
+int ssa_amd_summarize_pairs_xdrop(int mode, int64_t xdrop, const int64_t* band_lo, const int64_t* band_hi,
+                                  const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes,
+                                  const uint64_t* d_off, size_t npairs, ssa_amd_pair_summary_t* out) {
+    return summarize_pairs_xdrop(mode, xdrop, band_lo, band_hi, q_codes, q_off, d_codes, d_off, npairs, out);
+}
+
+uint64_t ssa_amd_get_xdrop_dropped(void) { return xdrop_dropped(); }
+
 size_t ssa_amd_map_residues(const char* ascii, size_t len, char* out, size_t cap) {
     const int st = cfg().symtype;
     const signed char* map = (st == AMINOACID || st == TRANS_QUERY) ? map_aa() : map_nt();

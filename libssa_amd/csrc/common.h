@@ -259,6 +259,18 @@ int align_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_hi, 
 int summarize_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* q_codes,
                           const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off, size_t npairs,
                           ssa_amd_pair_summary_t* out);
+// pairs_xdrop.cpp: ssa_amd_score_pairs_xdrop / ssa_amd_align_pairs_xdrop / ssa_amd_summarize_pairs_xdrop; the
+// same statistics, and the pairs of the last such call that met a drop row
+int score_pairs_xdrop(int mode, int64_t xdrop, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* q_codes,
+                      const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off, size_t npairs,
+                      int64_t* scores);
+int align_pairs_xdrop(int mode, int64_t xdrop, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* q_codes,
+                      const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off, size_t npairs,
+                      ssa_amd_pair_alignment_t* out, char* cigars, size_t cigar_cap);
+int summarize_pairs_xdrop(int mode, int64_t xdrop, const int64_t* band_lo, const int64_t* band_hi,
+                          const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off,
+                          size_t npairs, ssa_amd_pair_summary_t* out);
+uint64_t xdrop_dropped();
 void set_pairs_stats(const ssa_amd_pairs_stats_t& s);
 void set_align_pairs_stats(const ssa_amd_align_pairs_stats_t& s);
 

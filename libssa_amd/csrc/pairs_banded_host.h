@@ -1,5 +1,5 @@
 // pairs_banded_host.h -- the host side of the banded pair calls that the local
-// pair calls share (defined in pairs_banded.cpp; used by pairs_local.cpp and pairs_summary.cpp): the
+// pair calls share (defined in pairs_banded.cpp; used by pairs_local.cpp, pairs_summary.cpp and pairs_xdrop.cpp): the
 // band's clamp and validity rule, the batch ordered by shape and band with its
 // BandStrip ranges, the chunk packer and the device buffers it fills.  Host
 // code only.
@@ -8,6 +8,7 @@
 
 #include "pairs_banded.h"
 #include "pairs_host.h"
+#include "pairs_summary.h"
 
 namespace ssa {
 
@@ -87,5 +88,19 @@ bool local_host_align(int mode, const uint8_t* q, size_t ql, const uint8_t* d, s
 int local_canonical(int mode);
 bool local_bands_ok(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint64_t* qoff,
                     const uint64_t* doff, size_t n, std::vector<int64_t>& lo, std::vector<int64_t>& hi);
+
+// ------------------------------------ what the X-drop calls share (pairs_xdrop.cpp)
+// pairs_local.cpp: its host routines with the row rule of DESIGN.md §9.8 (mode: canonical, a local end without
+// a local begin; xdrop >= 0; both sides non-empty or not); dropped is set where the pair met a drop row.
+int64_t xdrop_host_score(int mode, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,
+                         int64_t xdrop, bool& dropped);
+bool xdrop_host_align(int mode, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,
+                      int64_t xdrop, ssa_amd_pair_alignment_t& o, char* text, bool& dropped);
+// pairs_summary.cpp: the chunk's summary buffers (SummaryArgs over K.A; *h_sum: the pinned twin of sum)
+SummaryArgs summary_chunk_args(const BandBatch& B, const BandChunk& K, int dev_id, const uint2** h_sum);
+// ... one device lane's record from its end cell and its words; true for the empty alignment under a local bit
+bool summary_record(bool local, int2 end, uint2 words, ssa_amd_pair_summary_t& o);
+// ... columns, matched and identical of a CIGAR text walked from (region[0], region[2]), added to o
+void summary_count_text(const char* text, const uint8_t* q, const uint8_t* d, ssa_amd_pair_summary_t& o);
 
 }  // namespace ssa

@@ -46,9 +46,15 @@ struct HostScratch {
 // dir) with the floor and kDirStop under a local begin and, under a local end,
 // the candidates of all existing real cells with a finite H -- greater, or
 // equal and the smaller (j, i).  The score is the end cell's H as it stands;
-// the caller takes max(0, score).
+// the caller takes max(0, score).  xdrop >= 0 (a local end without a local
+// begin): the candidates are cut row by row -- a row keeps its
+// greatest finite H and the smallest column that attains it; best starts at 0
+// with no end cell; a row whose maximum lies more than xdrop below best is the
+// drop row, the loop stops there and *dropped is set; else a greater maximum,
+// or an equal one in a smaller column than the end cell's, moves the end cell.
 EndCell host_local(int mode, const uint8_t* q, size_t qn, const uint8_t* d, size_t dn, int64_t lo, int64_t hi,
-                   const int64_t* M, int64_t Q, int64_t R, int64_t* h, int64_t* f, uint8_t* dir) {
+                   const int64_t* M, int64_t Q, int64_t R, int64_t* h, int64_t* f, uint8_t* dir, int64_t xdrop = -1,
+                   bool* dropped = nullptr) {
     const bool fqb = mode & kFreeQBegin, fqe = mode & kFreeQEnd, fdb = mode & kFreeDBegin, fde = mode & kFreeDEnd;
     const bool lb = mode & kLocalBegin, le = mode & kLocalEnd;
     const int64_t m = (int64_t)qn, n = (int64_t)dn, W = hi - lo + 1, goe = Q + R;
@@ -71,10 +77,12 @@ EndCell host_local(int mode, const uint8_t* q, size_t qn, const uint8_t* d, size
         h[j + 1 - lo] = v;
         f[j + 1 - lo] = (j >= 0 && v > kNeg / 2) ? v + goe : kNeg;
     }
-    int64_t row_best = INT64_MIN, col_best = INT64_MIN, best = INT64_MIN;
+    int64_t row_best = INT64_MIN, col_best = INT64_MIN, best = xdrop >= 0 ? 0 : INT64_MIN;
     size_t row_col = 0, col_row = 0;
     int64_t best_i = 0, best_j = 0;
+    bool have = false;                                   // under xdrop: an end cell exists
     for (int64_t i = 0; i < m; i++) {
+        int64_t row_m = kNeg, row_c = 0;                 // under xdrop: the row's greatest finite H, its first column
         const int64_t* srow = M + q[i];                  // M[d][q[i]] = srow[d << 5]
         const int64_t j1 = std::min(n - 1, i + hi);
         int64_t j = std::max<int64_t>(-1, i + lo);
@@ -104,6 +112,10 @@ EndCell host_local(int mode, const uint8_t* q, size_t qn, const uint8_t* d, size
             e = std::max(e2, t);
             f[k] = std::max(f2, t);
             if (le) {
+                if (xdrop >= 0) {
+                    if (hv > kNeg / 2 && hv > row_m) row_m = hv, row_c = j;
+                    continue;
+                }
                 // rows ascend: an equal cell wins only from a smaller column
                 if (hv > kNeg / 2 && (hv > best || (hv == best && j < best_j))) {
                     best = hv;
@@ -120,6 +132,18 @@ EndCell host_local(int mode, const uint8_t* q, size_t qn, const uint8_t* d, size
             if (fqe && j == n - 1 && hv >= col_best) {
                 col_best = hv;
                 col_row = (size_t)i;
+            }
+        }
+        if (xdrop >= 0 && row_m > kNeg / 2) {
+            if (best - row_m > xdrop) {
+                if (dropped) *dropped = true;
+                break;
+            }
+            if (row_m > best || (row_m == best && have && row_c < best_j)) {
+                best = row_m;
+                best_i = i;
+                best_j = row_c;
+                have = true;
             }
         }
     }
@@ -176,18 +200,18 @@ void empty_alignment(ssa_amd_pair_alignment_t& o, char* text) {
 }
 
 int64_t host_score(int mode, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,
-                   HostScratch& S) {
+                   HostScratch& S, int64_t xdrop = -1, bool* dropped = nullptr) {
     if (ql == 0 || dl == 0) return 0;       // ends_empty_score of a canonical mode with a local bit
     const size_t W = (size_t)(hi - lo + 1);
     if (S.h.size() < W + 1) S.h.resize(W + 1), S.f.resize(W + 1);
     const EndCell c = host_local(mode, q, ql, d, dl, lo, hi, matrix().m, cfg().gap_open, cfg().gap_extend, S.h.data(),
-                                 S.f.data(), nullptr);
+                                 S.f.data(), nullptr, xdrop, dropped);
     return std::max<int64_t>(c.score, 0);
 }
 
 // returns true for the empty alignment of two non-empty sides
 bool host_align(int mode, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,
-                HostScratch& S, ssa_amd_pair_alignment_t& o, char* text) {
+                HostScratch& S, ssa_amd_pair_alignment_t& o, char* text, int64_t xdrop = -1, bool* dropped = nullptr) {
     o.flags = 1;
     if (ql == 0 || dl == 0) {
         empty_alignment(o, text);
@@ -197,7 +221,7 @@ bool host_align(int mode, const uint8_t* q, size_t ql, const uint8_t* d, size_t 
     if (S.h.size() < W + 1) S.h.resize(W + 1), S.f.resize(W + 1);
     if (S.dir.size() < ql * W) S.dir.resize(ql * W);
     const EndCell c = host_local(mode, q, ql, d, dl, lo, hi, matrix().m, cfg().gap_open, cfg().gap_extend, S.h.data(),
-                                 S.f.data(), S.dir.data());
+                                 S.f.data(), S.dir.data(), xdrop, dropped);
     if (c.score <= 0) {
         empty_alignment(o, text);
         return true;
@@ -253,6 +277,19 @@ bool local_host_align(int mode, const uint8_t* q, size_t ql, const uint8_t* d, s
                       ssa_amd_pair_alignment_t& o, char* text) {
     HostScratch S;
     return host_align(mode, q, ql, d, dl, lo, hi, S, o, text);
+}
+
+// ---- shared with pairs_xdrop.cpp (pairs_banded_host.h): the routines above with the row rule
+int64_t xdrop_host_score(int mode, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,
+                         int64_t xdrop, bool& dropped) {
+    HostScratch S;
+    return host_score(mode, q, ql, d, dl, lo, hi, S, xdrop, &dropped);
+}
+
+bool xdrop_host_align(int mode, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,
+                      int64_t xdrop, ssa_amd_pair_alignment_t& o, char* text, bool& dropped) {
+    HostScratch S;
+    return host_align(mode, q, ql, d, dl, lo, hi, S, o, text, xdrop, &dropped);
 }
 
 int score_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* qc,

@@ -62,6 +62,24 @@ bool host_summary(int mode, const uint8_t* q, size_t ql, const uint8_t* d, size_
     return zero;
 }
 
+// One device pair's record from its end cell and its words; true for the empty alignment under a local bit.
+bool record_of(bool local, const int2 e, const uint2 w, ssa_amd_pair_summary_t& o) {
+    o = ssa_amd_pair_summary_t{};
+    if (local && e.x <= 0) return true;
+    const uint32_t pos = (uint32_t)e.y;
+    o.score = e.x;
+    o.region[0] = w.y >> 16;
+    o.region[1] = pos & 0xffff;
+    o.region[2] = w.y & 0xffff;
+    o.region[3] = pos >> 16;
+    o.matched = w.x & 0xffff;
+    o.identical = w.x >> 16;
+    // every M column spans one row and one column, every gap column one of the two
+    o.columns = (uint32_t)((int64_t)(o.region[1] - o.region[0] + 1) + (int64_t)(o.region[3] - o.region[2] + 1) -
+                           (int64_t)o.matched);
+    return false;
+}
+
 // the row buffer of the words and the lanes' summary words, kept between calls beside banded_device()'s
 struct SummaryDevice {
     int device = -1;
@@ -88,6 +106,21 @@ SummaryArgs summary_args(const BandBatch& B, const BandChunk& K, int dev_id) {
 }
 
 }  // namespace
+
+// ---- shared with pairs_xdrop.cpp (pairs_banded_host.h)
+SummaryArgs summary_chunk_args(const BandBatch& B, const BandChunk& K, int dev_id, const uint2** h_sum) {
+    const SummaryArgs A = summary_args(B, K, dev_id);
+    *h_sum = (const uint2*)g_dev.sum.h;
+    return A;
+}
+
+bool summary_record(bool local, int2 end, uint2 words, ssa_amd_pair_summary_t& o) {
+    return record_of(local, end, words, o);
+}
+
+void summary_count_text(const char* text, const uint8_t* q, const uint8_t* d, ssa_amd_pair_summary_t& o) {
+    count_text(text, q, d, o);
+}
 
 int summarize_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_hi, const uint8_t* qc,
                           const uint64_t* qoff, const uint8_t* dc, const uint64_t* doff, size_t n,
@@ -176,27 +209,8 @@ int summarize_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_
             const int2* h_out = (const int2*)P.out.h;
             const uint2* h_sum = (const uint2*)g_dev.sum.h;
             uint64_t z = 0;
-            for (size_t p = K.p0; p < K.p1; p++) {
-                const int2 e = h_out[p - K.p0];
-                const uint2 w = h_sum[p - K.p0];
-                ssa_amd_pair_summary_t& o = out[B.idx[p]];
-                o = ssa_amd_pair_summary_t{};
-                if (local && e.x <= 0) {
-                    z++;
-                    continue;
-                }
-                const uint32_t pos = (uint32_t)e.y;
-                o.score = e.x;
-                o.region[0] = w.y >> 16;
-                o.region[1] = pos & 0xffff;
-                o.region[2] = w.y & 0xffff;
-                o.region[3] = pos >> 16;
-                o.matched = w.x & 0xffff;
-                o.identical = w.x >> 16;
-                // every M column spans one row and one column, every gap column one of the two
-                o.columns = (uint32_t)((int64_t)(o.region[1] - o.region[0] + 1) +
-                                       (int64_t)(o.region[3] - o.region[2] + 1) - (int64_t)o.matched);
-            }
+            for (size_t p = K.p0; p < K.p1; p++)
+                z += record_of(local, h_out[p - K.p0], h_sum[p - K.p0], out[B.idx[p]]);
             zeros += z;
             S.chunks++;
             g0 = K.g1;
