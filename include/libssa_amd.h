@@ -197,6 +197,9 @@ uint32_t ssa_amd_get_pruned_whole( void );
  *   "sw_kernel" 0|1      1: int16 strip kernel instead of the pair kernel
  *   "force_wide" 0|1     1: every entry through the int64 kernel
  *   "no_filter" 0|1      1: copy every score back (no device top-k filter)
+ *   "above_filter" 1|0   ssa_amd_search_above: 1 (default) the device forwards only the scores at or
+ *                        above the threshold; 0: every score is copied back and the host scans them
+ *                        (the same list; also what "no_filter" 1 or a query view without rows gets)
  *   "long_groups" -1|0|N leading groups scored one entry per wave: auto, never, N
  *   "long_share_pct" P   auto threshold: P % of one SIMD's share of all columns
  *   "long_waves" 0|4|1   waves scoring one long entry (its query rows split over
@@ -321,6 +324,40 @@ size_t ssa_amd_search( p_query query, int algo, size_t hitcount, int bit_width, 
  * (DESIGN.md §7). */
 size_t ssa_amd_search_batch( const p_query * queries, size_t nq, int algo, size_t hitcount, int bit_width,
                              ssa_hit_t * out, size_t * counts );
+
+/* Every (query view, DB entry) of the open DB whose exact score is >= min_score
+ * -- where the calls above return the k best.  algo: SSA_AMD_SW or SSA_AMD_NW;
+ * bit_width as in ssa_amd_search (scores are exact at every width, the width
+ * only decides the overflow counters).  Each hit's score is what sw_align /
+ * nw_align report for that (view, entry), db_id is global
+ * (ssa_amd_set_id_offset), query_id / db_strand / db_frame as ssa_amd_search
+ * fills them.  *total (may be NULL) receives the number of qualifying hits;
+ * the return value is the number written, min(total, cap): the FIRST cap hits
+ * of the full list in the order
+ *   score descending, then db_id descending (sw_align's order: the list
+ *   continues a top-k list), then query_id, db_strand, db_frame ascending.
+ * out == NULL or cap == 0 counts only.  min_score is any int64 (NW thresholds
+ * may be negative); SW with min_score <= 0 returns every entry, a threshold
+ * above every score returns 0.  A NULL query and configuration errors behave
+ * as in ssa_amd_search.  The call never prunes and never merges rare codes
+ * (stats pruned_units, inplace_units, pruned_first, rare_merged and
+ * ssa_amd_get_pruned_whole() read 0; part_units may not): every score it
+ * compares is exact.  ssa_amd_get_stats reports it as a search;
+ * filter_candidates is the number of (position, score) pairs that crossed PCIe
+ * (option "above_filter").  With several device slots (ssa_amd_set_devices,
+ * SSA_AMD_DEVICES) each searches its shard and the lists are merged: the
+ * result is that of one device. */
+size_t ssa_amd_search_above( p_query query, int algo, int64_t min_score, int bit_width,
+                             ssa_hit_t * out, size_t cap, size_t * total );
+
+/* Host only: the threshold, order and cut of ssa_amd_search_above applied to
+ * any n hits -- the concatenated lists of a sharded caller's ranks, each
+ * searched with its own ssa_amd_set_id_offset (the counterpart of
+ * ssa_amd_replay for threshold lists).  No device and no DB are involved.
+ * Returns the number written, min(*total, cap); out == NULL or cap == 0
+ * counts only. */
+size_t ssa_amd_merge_above( const ssa_hit_t * hits, size_t n, int64_t min_score,
+                            ssa_hit_t * out, size_t cap, size_t * total );
 
 /* Replays an insertion log (concatenated shard logs, in shard order) and
  * writes the sorted top-k (score desc, id desc).  Returns the count. */

@@ -128,7 +128,7 @@ EXPORTS = {
                       "ssa_amd_prune_start_order", "ssa_amd_get_pruned_whole", "ssa_amd_align_hits",
                       "ssa_amd_get_align_hits_stats", "ssa_amd_summarize_pairs_local",
                       "ssa_amd_score_pairs_xdrop", "ssa_amd_align_pairs_xdrop", "ssa_amd_summarize_pairs_xdrop",
-                      "ssa_amd_get_xdrop_dropped"],
+                      "ssa_amd_get_xdrop_dropped", "ssa_amd_search_above", "ssa_amd_merge_above"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -161,6 +161,10 @@ def load():
         "ssa_amd_get_stats": ([POINTER(ssa_amd_stats_t)], None), "ssa_amd_set_option": ([c_char_p, c_long], None),
         "ssa_amd_search": ([P, c_int, c_size_t, c_int, c_int, POINTER(ssa_hit_t), c_size_t], c_size_t),
         "ssa_amd_replay": ([POINTER(ssa_hit_t), c_size_t, c_size_t, POINTER(ssa_hit_t)], c_size_t),
+        "ssa_amd_search_above": ([P, c_int, c_int64, c_int, POINTER(ssa_hit_t), c_size_t, POINTER(c_size_t)],
+                                 c_size_t),
+        "ssa_amd_merge_above": ([POINTER(ssa_hit_t), c_size_t, c_int64, POINTER(ssa_hit_t), c_size_t,
+                                 POINTER(c_size_t)], c_size_t),
         "ssa_amd_query_views": ([P, POINTER(q_seq_t), c_size_t], c_size_t),
         "ssa_amd_save_db": ([c_char_p], c_int), "ssa_amd_load_db": ([c_char_p], c_int),
         "ssa_amd_set_devices": ([POINTER(c_int), c_int], c_int),
@@ -394,6 +398,56 @@ def search(q, algo, hitcount, bit_width=BIT_WIDTH_16, mode=TOPK, cap=None):
             break
         cap *= 4            # a log filled the buffer: search again with room
     return [(buf[i].score, buf[i].db_id, buf[i].query_id, buf[i].db_strand, buf[i].db_frame) for i in range(n)]
+
+
+def _above_args(min_score, cap):
+    if isinstance(min_score, bool) or not isinstance(min_score, int):
+        raise TypeError(f"min_score must be an int, not {type(min_score).__name__}")
+    if not -2 ** 63 <= min_score < 2 ** 63:
+        raise OverflowError(f"min_score {min_score} is no int64")
+    if cap is not None and (isinstance(cap, bool) or not isinstance(cap, int)):
+        raise TypeError(f"cap must be an int or None, not {type(cap).__name__}")
+    if cap is not None and cap < 0:
+        raise ValueError(f"cap must be >= 0, not {cap}")
+
+
+def _hit_tuples(buf, n):
+    return [(buf[i].score, buf[i].db_id, buf[i].query_id, buf[i].db_strand, buf[i].db_frame) for i in range(n)]
+
+
+def search_above(q, algo, min_score, bit_width=BIT_WIDTH_16, cap=None):
+    """ssa_amd_search_above: (hits, total) -- every (view, entry) of the open
+    DB scoring at least min_score as (score, global_id, query_id, strand,
+    frame), best first, and their number.  cap: at most that many hits (the
+    first of the full list; 0 counts only); None: count first, then fetch all
+    -- two whole searches, so pass a cap where an upper bound is known."""
+    _above_args(min_score, cap)
+    L = load()
+    total = c_size_t(0)
+    if cap is None or cap == 0:
+        L.ssa_amd_search_above(q, algo, min_score, bit_width, None, 0, ctypes.byref(total))
+        if cap == 0 or total.value == 0:
+            return [], total.value
+        cap = total.value
+    buf = _hits(cap)
+    n = L.ssa_amd_search_above(q, algo, min_score, bit_width, buf, cap, ctypes.byref(total))
+    return _hit_tuples(buf, n), total.value
+
+
+def merge_above(hits, min_score, cap=None):
+    """ssa_amd_merge_above: (hits, total) -- the hits of a (concatenated)
+    list of hit tuples at or above min_score in search_above's order, cut to
+    cap (None: all), and their number before the cut.  Host only."""
+    _above_args(min_score, cap)
+    L = load()
+    n = len(hits)
+    arr = _hit_array(hits)
+    total = c_size_t(0)
+    if cap is None:
+        cap = n
+    out = (ssa_hit_t * max(cap, 1))()
+    c = L.ssa_amd_merge_above(arr, n, min_score, out, cap, ctypes.byref(total))
+    return _hit_tuples(out, c), total.value
 
 
 def replay(log, hitcount):

@@ -284,6 +284,9 @@ void publish_stats(const std::vector<SearchScores>& sc, const std::vector<SlotPl
     }
 }
 
+void finish_search(const std::vector<SearchScores>& sc, const std::vector<SlotPlan>& plan,
+                   const std::vector<double>& slot_ms, int bw, double t0, double t1, double t2);
+
 void run_search(p_query q, int algo, size_t k, int bw, bool want_log, SearchResult& R) {
     const double t0 = now_ms();
     check_width(bw);
@@ -333,7 +336,14 @@ void run_search(p_query q, int algo, size_t k, int bw, bool want_log, SearchResu
                 if (heap.add(h) && want_log) R.hits.push_back(h);
     }
     if (!want_log) R.hits = heap.sorted();
-    const double t2 = now_ms();
+    finish_search(sc, plan, slot_ms, bw, t0, t1, now_ms());
+}
+
+// What every search call ends with: the statistics (t0 the call's start, t1
+// the end of the device searches, t2 the end of the host's list building) and
+// m_run's bookkeeping messages.
+void finish_search(const std::vector<SearchScores>& sc, const std::vector<SlotPlan>& plan,
+                   const std::vector<double>& slot_ms, int bw, double t0, double t1, double t2) {
     // the reference's overflow counters, counted on the device
     // (counters.hip): what its 8/16-bit kernels would have re-run
     uint64_t o8 = 0, o16 = 0;
@@ -369,6 +379,93 @@ void run_search(p_query q, int algo, size_t k, int bw, bool want_log, SearchResu
     if (records != entries)
         print_warning("# Number of processed sequences differs! Expected: %ld - Actual: %ld\n", (long)records,
                       (long)entries);
+}
+
+// The threshold calls' total order (ssa_amd_search_above, ssa_amd_merge_above):
+// score descending, then ID descending -- sort_hits' rule, so the list continues
+// a top-k list -- then query view, DB strand and DB frame ascending.
+bool above_before(const Hit& a, const Hit& b) {
+    if (a.score != b.score) return a.score > b.score;
+    if (a.id != b.id) return a.id > b.id;
+    if (a.qid != b.qid) return a.qid < b.qid;
+    if (a.strand != b.strand) return a.strand < b.strand;
+    return a.frame < b.frame;
+}
+
+// The first cap hits of v in that order (v itself when it holds no more).
+void order_and_cut(std::vector<Hit>& v, size_t cap) {
+    if (cap < v.size()) {
+        // (a cut far below the total: only the kept part is ordered)
+        if (cap < v.size() / 8) std::partial_sort(v.begin(), v.begin() + cap, v.end(), above_before);
+        else std::sort(v.begin(), v.end(), above_before);
+        v.resize(cap);
+    } else {
+        std::sort(v.begin(), v.end(), above_before);
+    }
+}
+
+// The hits of `hits` at or above min_score, ordered and cut to cap; *total
+// receives their number before the cut.
+std::vector<Hit> merge_above(const std::vector<Hit>& hits, int64_t min_score, size_t cap, size_t* total) {
+    std::vector<Hit> v;
+    for (const Hit& h : hits)
+        if (h.score >= min_score) v.push_back(h);
+    if (total) *total = v.size();
+    order_and_cut(v, cap);
+    return v;
+}
+
+// One slot's hits at or above min_score, unordered: the entries the select
+// kernel forwarded (a superset: overflowed lanes, the 32-bit clamp), or every
+// score of a search that copied all of them back.
+void collect_above(const SearchScores& sc, const EntryMeta& meta, int64_t min_score, std::vector<Hit>& hits) {
+    const size_t E = sc.entries;
+    const uint64_t off = cfg().id_offset;
+    auto visit = [&](size_t v, size_t e) {
+        const int32_t x = sc.s32[v * E + e];
+        if (x != INT32_MIN && x < min_score) return;
+        const int64_t s = sc.get(v, e);
+        if (s >= min_score) hits.push_back(Hit{s, meta.id[e] + off, (uint8_t)v, meta.strand[e], meta.frame[e]});
+    };
+    if (sc.sparse) {
+        for (const uint32_t x : sc.cand) visit(x / E, x % E);
+        return;
+    }
+    for (size_t v = 0; v < sc.views; v++)
+        for (size_t e = 0; e < E; e++) visit(v, e);
+}
+
+// ssa_amd_search_above: run_search's counterpart.  Every slot searches its
+// shard with the threshold (device_search's `above`) and collects its hits,
+// on its pool thread; the slots' lists go through merge_above together.
+std::vector<Hit> run_search_above(p_query q, int algo, int64_t min_score, int bw, size_t cap, size_t* total) {
+    const double t0 = now_ms();
+    check_width(bw);
+    ensure_device_db();
+    const std::vector<SlotPlan> plan = device_plan();
+    const std::vector<QueryView> views = query_views(q);
+    std::vector<SearchScores> sc(plan.size());
+    std::vector<std::vector<Hit>> lists(plan.size());
+    std::vector<double> slot_ms(plan.size(), 0.0);
+    double t1;
+    if (plan.size() == 1) {
+        device_search(device_db(0), views, algo, 0, bw, sc[0], nullptr, false, &min_score);
+        slot_ms[0] = now_ms() - t0;
+        t1 = now_ms();
+        collect_above(sc[0], device_db(0).meta, min_score, lists[0]);
+    } else {
+        slot_pool().run(plan.size(), [&](size_t s) {
+            const double ts = now_ms();
+            device_search(device_db(s), views, algo, 0, bw, sc[s], nullptr, false, &min_score);
+            collect_above(sc[s], device_db(s).meta, min_score, lists[s]);
+            slot_ms[s] = now_ms() - ts;
+        });
+        t1 = now_ms();
+        for (size_t s = 1; s < plan.size(); s++) lists[0].insert(lists[0].end(), lists[s].begin(), lists[s].end());
+    }
+    std::vector<Hit> hits = merge_above(lists[0], min_score, cap, total);
+    finish_search(sc, plan, slot_ms, bw, t0, t1, now_ms());
+    return hits;
 }
 
 // create_score_alignment_list (aligner.c:62-99): one alignment_t per hit,
@@ -798,6 +895,7 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "force_wide")) cfg().force_wide = (int)value;
     else if (!strcmp(name, "sw_kernel")) cfg().sw_kernel = (int)value;
     else if (!strcmp(name, "no_filter")) cfg().no_filter = (int)value;
+    else if (!strcmp(name, "above_filter")) cfg().above_filter = (int)value;
     else if (!strcmp(name, "pair_np")) cfg().pair_np = (int)value;
     else if (!strcmp(name, "long_groups")) cfg().long_groups = (int)value;
     else if (!strcmp(name, "long_share_pct")) cfg().long_share_pct = (int)value;
@@ -997,6 +1095,28 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
     S.kernel_launches = launches;
     S.search_ms = now_ms() - t0;
     return total;
+}
+
+size_t ssa_amd_search_above(p_query query, int algo, int64_t min_score, int bit_width, ssa_hit_t* out, size_t cap,
+                            size_t* total) {
+    test_configuration(query);
+    if (!out) cap = 0;
+    const std::vector<Hit> v = run_search_above(query, algo == SSA_AMD_NW ? kAlgoNW : kAlgoSW, min_score, bit_width,
+                                                cap, total);
+    for (size_t i = 0; i < v.size(); i++)
+        out[i] = ssa_hit_t{v[i].score, v[i].id, v[i].qid, v[i].strand, v[i].frame, {0, 0, 0, 0, 0}};
+    return v.size();
+}
+
+size_t ssa_amd_merge_above(const ssa_hit_t* hits, size_t n, int64_t min_score, ssa_hit_t* out, size_t cap,
+                           size_t* total) {
+    std::vector<Hit> in;
+    for (size_t i = 0; hits && i < n; i++)
+        in.push_back(Hit{hits[i].score, hits[i].db_id, hits[i].query_id, hits[i].db_strand, hits[i].db_frame});
+    const std::vector<Hit> v = merge_above(in, min_score, out ? cap : 0, total);
+    for (size_t i = 0; i < v.size(); i++)
+        out[i] = ssa_hit_t{v[i].score, v[i].id, v[i].qid, v[i].strand, v[i].frame, {0, 0, 0, 0, 0}};
+    return v.size();
 }
 
 size_t ssa_amd_replay(const ssa_hit_t* log, size_t n, size_t hitcount, ssa_hit_t* out) {

@@ -1424,7 +1424,8 @@ std::vector<uint32_t> prune_start_order(const uint32_t* ncols, uint32_t ngroups,
 // of that launch are not used and the caller runs the search again without
 // parts.
 static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views, int algo, size_t k, int bw,
-                               SearchScores& out, std::vector<SearchScores>* indep, bool no_parts, bool allow_prune) {
+                               SearchScores& out, std::vector<SearchScores>* indep, bool no_parts, bool allow_prune,
+                               const int64_t* above) {
     check(hipSetDevice(D.device), "hipSetDevice");
     const Config& C = cfg();
     const size_t E = D.meta.size();
@@ -1491,6 +1492,13 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     // covers at most kFilterMaxViews)
     out.sparse = (indep != nullptr || V <= (size_t)kFilterMaxViews) && k > 0 && k <= (size_t)kFilterMaxK && E > 0 &&
                  all_rows && !cfg().no_filter;
+    // a threshold search (above.h): the select kernel forwards the scores at
+    // or above the threshold, whatever their number -- k plays no part; option
+    // "above_filter" 0 copies every score back instead (the A/B and fallback)
+    if (above) {
+        if (indep) fatal("device_search: a threshold search has no batch mode");
+        out.sparse = V <= (size_t)kFilterMaxViews && E > 0 && all_rows && !cfg().no_filter && cfg().above_filter;
+    }
     // several views: enqueued back to back (host preparation of view v+1
     // overlaps view v on the GPU), each into its own score and overflow
     // slice, then one filter pass over all (view, entry) scores in the
@@ -1501,11 +1509,13 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     const bool ind = indep != nullptr;
     if (ind && !(out.sparse && V > 1 && V <= kMaxBatchPipe)) fatal("device_search: batch not pipelinable");
     const bool multi = out.sparse && V > 1 && !ind;
+    // (a threshold has no insertion order: its positions are view * E + entry)
+    const bool ordered = multi && !above;
     const bool piped = multi || ind;
     const bool lean = C.lean_events != 0;   // (option "lean_events": no upload/tier/filter markers)
     // the rare-code merge (plan_view) needs the single-pass filter and no
     // counters (they decide from exact scores)
-    const bool allow_merge = C.rare_merge && V == 1 && !ind && out.sparse && !want_counts && E > 0;
+    const bool allow_merge = C.rare_merge && V == 1 && !ind && out.sparse && !want_counts && E > 0 && !above;
     if (allow_merge && D.alpha > 21) ensure_entry_masks(D);
     // every lane fits a view's overflow list (reference: no limit on the
     // sequences search_16.c:101-109 re-runs at 64 bits)
@@ -1545,7 +1555,15 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
         }
         indep->assign(V, SearchScores{});
     }
-    if (multi) {
+    if (multi && above) {
+        // the select pass needs the candidate buffer alone, none of the
+        // top-k filter's scratch (a later top-k search sizes that itself)
+        if (D.fbuf_bytes < kFilterHeader * 4 + V * E * 8) {
+            dfree(D.d_fbuf);
+            check(hipMalloc((void**)&D.d_fbuf, kFilterHeader * 4 + V * E * 8), "filter candidates");
+            D.fbuf_bytes = kFilterHeader * 4 + V * E * 8;
+        }
+    } else if (multi) {
         if (D.filter_cap < V * E) {
             const size_t nb = (V * E + kFilterBlock - 1) / kFilterBlock;
             dfree(D.d_fbuf); dfree(D.d_summary); dfree(D.d_before); dfree(D.d_thresh_local); dfree(D.d_thresh);
@@ -2672,6 +2690,27 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
         if (!lean) check(hipEventRecord(D.ev[2], st), "event");
         if (ind) {
             // (filters already enqueued per query)
+        } else if (above && out.sparse) {
+            // the threshold's select pass in the filter's place: the same
+            // header, the candidates in the same buffer (above.h)
+            AboveArgs f{};
+            f.scores = D.d_scores;
+            f.n = (uint32_t)(multi ? V * E : E);
+            f.t32 = above_t32(*above);
+            f.ovf_count = D.d_ovf;
+            f.ovf_stride = (uint32_t)(ovf_capv + 1);
+            f.nviews = (uint32_t)(multi ? V : 1);
+            f.counters = D.d_fbuf;
+            f.status = gate + 2;
+            f.cand = (uint2*)(D.d_fbuf + kFilterHeader);
+            check(launch_above(f, st), "threshold select launch");
+            // the first copy sized by the last threshold search's count (the
+            // top-k search's hint, D.cand_hint, is left alone)
+            const size_t first = std::min<size_t>(std::min<size_t>(D.h_cand_cap, f.n),
+                                                  std::max<size_t>(256, 2 * (size_t)D.above_hint + 64));
+            D.cand_first = first;
+            check(hipMemcpyAsync(D.h_fbuf, D.d_fbuf, kFilterHeader * 4 + 8 * first, hipMemcpyDeviceToHost, st),
+                  "D2H candidates");
         } else if (out.sparse) {
             FilterArgs f{};
             f.scores = D.d_scores;
@@ -2855,7 +2894,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             const uint32_t nc = D.h_fbuf[0];
             const uint2* cand = (const uint2*)(D.h_fbuf + kFilterHeader);
             std::vector<uint2> more;
-            D.cand_hint = nc;
+            (above ? D.above_hint : D.cand_hint) = nc;
             if (want_prune) {
                 out.pruned_units = D.h_fbuf[4];
                 out.inplace_units = D.h_fbuf[5];
@@ -2873,10 +2912,11 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             out.cand.resize(nc);
             for (uint32_t i = 0; i < nc; i++) {
                 out.cand[i] = cand[i].x;
-                D.h_scores[multi ? D.h_order[cand[i].x] : cand[i].x] = (int32_t)cand[i].y;
+                D.h_scores[ordered ? D.h_order[cand[i].x] : cand[i].x] = (int32_t)cand[i].y;
             }
-            std::sort(out.cand.begin(), out.cand.end());
-            if (multi)
+            // (a threshold's list is ordered by score later: its positions stay as they came)
+            if (!above) std::sort(out.cand.begin(), out.cand.end());
+            if (ordered)
                 for (uint32_t i = 0; i < nc; i++) out.cand[i] = D.h_order[out.cand[i]];
             for (size_t vv = 0; vv < (multi ? V : 1); vv++) {
                 const uint32_t nov = D.h_fbuf[3 + vv];
@@ -2981,14 +3021,15 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
 }
 
 void device_search(DeviceDB& D, const std::vector<QueryView>& views, int algo, size_t k, int bw, SearchScores& out,
-                   std::vector<SearchScores>* indep, bool allow_prune) {
-    if (device_search_once(D, views, algo, k, bw, out, indep, false, allow_prune)) {
+                   std::vector<SearchScores>* indep, bool allow_prune, const int64_t* above) {
+    if (above) allow_prune = false;      // (a threshold search observes every exact score)
+    if (device_search_once(D, views, algo, k, bw, out, indep, false, allow_prune, above)) {
         out.part_retries = 0;
         return;
     }
     // (every stream of the search has been synchronised; the counters and
     // the wait flag are zeroed again at the start of the search)
-    if (!device_search_once(D, views, algo, k, bw, out, indep, true, false))
+    if (!device_search_once(D, views, algo, k, bw, out, indep, true, false, above))
         fatal("pair kernel: strip-part wait timed out with strip parts off");
     out.part_retries = 1;
 }

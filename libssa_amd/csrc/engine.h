@@ -6,6 +6,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "above.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -50,6 +51,7 @@ struct DeviceDB {
     size_t h_cand_cap = 0;
     size_t cand_first = 0;                // candidates the last single-view search copied with its counters
     uint32_t cand_hint = 0;               // the last single-view search's candidate count (sizes that copy)
+    uint32_t above_hint = 0;              // ... and the last threshold search's (ssa_amd_search_above), kept apart
     uint8_t* h_up = nullptr;              // pinned staging for per-search uploads
     size_t h_up_cap = 0;
     int32_t* d_scores = nullptr;
@@ -208,8 +210,9 @@ std::vector<uint8_t> fetch_entry_codes(uint64_t local_id, int strand, int frame)
 struct SearchScores {
     const int32_t* s32 = nullptr;
     size_t entries = 0, views = 0;
-    // sparse: only the entries in `cand` (ascending) were copied back -- the
-    // device filter proved every other entry leaves the top-k heap unchanged;
+    // sparse: only the entries in `cand` (ascending; a threshold search's in
+    // no order) were copied back -- the device filter proved every other
+    // entry leaves the top-k heap unchanged (or lies below the threshold);
     // o8/o16 then come from the device counters (non-overflowed entries)
     bool sparse = false;
     std::vector<uint32_t> cand;
@@ -250,8 +253,15 @@ struct SearchScores {
 // allow_prune: the caller replays `out` alone into one sorted top-k list, so
 // the pair kernel may skip strip parts that cannot reach it (option
 // "topk_prune"; api.cpp run_search)
+// above != null: a threshold search (ssa_amd_search_above): every (view,
+// entry) scoring at least *above comes back -- through above.h's select
+// kernel (out.sparse, out.cand = view * entries + entry in no order, a superset the
+// caller re-checks at 64 bits), or, with option "above_filter" 0, option
+// "no_filter" 1 or a query view without rows, as the full score vector.  k
+// is not used; nothing is pruned, merged or ordered
 void device_search(DeviceDB& D, const std::vector<QueryView>& views, int algo, size_t k, int bw, SearchScores& out,
-                   std::vector<SearchScores>* indep = nullptr, bool allow_prune = false);
+                   std::vector<SearchScores>* indep = nullptr, bool allow_prune = false,
+                   const int64_t* above = nullptr);
 bool batch_pipelinable(size_t nqueries, size_t k);
 // engine.cpp: part-0 ticket -> unit of a pruned search (option "prune_order")
 std::vector<uint32_t> prune_start_order(const uint32_t* ncols, uint32_t ngroups, size_t m, uint32_t pct, uint32_t cap);
