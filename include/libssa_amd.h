@@ -854,6 +854,59 @@ int ssa_amd_summarize_pairs_xdrop( int mode, int64_t xdrop, const int64_t * band
                                    size_t npairs, ssa_amd_pair_summary_t * out );
 uint64_t ssa_amd_get_xdrop_dropped( void );
 
+/* ssa_amd_summarize_pairs_local for search hits: out[i] is,
+ * field for field, what ssa_amd_summarize_pairs_local( mode, NULL, NULL, ... )
+ * returns under the current matrix and penalties for the pair
+ *   q side: the query view hits[i].query_id of `query` (ssa_amd_query_views' codes),
+ *   d side: the DB entry (db_id - ID offset, db_strand, db_frame) AS THE SEARCH
+ *           SCORED IT: the codes the packed DB holds for that entry.
+ * For NUCLEOTIDE with the complementary strand the d side of a strand-1 hit is
+ * the record's reverse complement.  This differs from ssa_amd_align_hits, which
+ * keeps the reference aligner's behaviour and aligns the record's FORWARD copy
+ * for such a hit (aligner.c:76 never flips it), so that call's text does not
+ * belong to the score the search reported; this call's summary does.
+ * hits are as ssa_amd_search, ssa_amd_search_batch and ssa_amd_search_above
+ * write them; hits[i].score is not read: out[i].score is the DP's own score, so
+ * under mode 63 it equals what sw_align reported for the hit and under mode 0
+ * what nw_align reported.  All 64 modes are accepted, through their canonical
+ * ones; the call is unbanded.  flags bit 0: summarized on the int64 host path.
+ * Returns non-zero, with nothing written and nothing launched, for a NULL
+ * query, a mode outside 0..63, NULL hits or out with n > 0, a db_id outside the
+ * open DB's ID range, a query_id that is not one of the query's views,
+ * db_strand > 1 or db_frame > 2, or a (record, strand, frame) no entry exists
+ * for (an empty record has no entry).  n == 0 returns 0; duplicates are fine.
+ * Routing.  A hit is GATHERED when option "hits_gather" is 1, a gfx950 device
+ * is visible, the search runs on one device slot (the pair calls' device), the
+ * packed DB is current there (it is packed when it is not) and the pair meets
+ * ssa_amd_summarize_pairs_local's device conditions.  Only a 16-byte
+ * descriptor per hit, the tables of a chunk and the query views are uploaded:
+ * hits_gather_kernel writes the summary kernels' lane-interleaved input from
+ * the device copy of the DB, translating its compact codes back to residue
+ * codes, directly in front of the unchanged summary kernels on the same stream.
+ * Every other hit is FETCHED: its entry codes are produced on the host as the
+ * packer produces them and the pair goes through ssa_amd_summarize_pairs_local
+ * itself (its device path, or its int64 host path under "pairs_host" 1 or
+ * without a device).  With several device slots (ssa_amd_set_devices,
+ * SSA_AMD_DEVICES) every hit is fetched: each slot holds a shard only.
+ * The results are identical either way.
+ * Statistics: ssa_amd_get_align_pairs_stats reports the call as the summary
+ * call does; when hits were gathered, kernels =
+ * "hits_gather,pairs_summary_end,pairs_summary_sweep" and launches = 3 x chunks
+ * of the gather path (+ 2 x chunks of the fetched rest).  ssa_amd_get_stats
+ * (the last search) is left alone.  Options:
+ *   "hits_gather" 1|0    1 (default): as above; 0: every hit is fetched
+ *   "pairs_chunk", "pairs_host" as for ssa_amd_summarize_pairs_local */
+typedef struct {
+    uint64_t hits;          /* hits of the last ssa_amd_summarize_hits call */
+    uint64_t gathered;      /* ... whose sequences the device packer took from the device copy of the DB */
+    uint64_t fetched;       /* ... fetched through the DB plugin on the host (hits = gathered + fetched) */
+    uint64_t upload_bytes;  /* bytes of descriptors, tables and query views uploaded on the gather path */
+    double   gather_ms;     /* HIP-event time of the hits_gather_kernel launches */
+} ssa_amd_hits_stats_t;
+int ssa_amd_summarize_hits( p_query query, int mode, const ssa_hit_t * hits, size_t n,
+                            ssa_amd_pair_summary_t * out );
+void ssa_amd_get_summarize_hits_stats( ssa_amd_hits_stats_t * out );
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,11 @@ assert ctypes.sizeof(alignment_t) == 112 and ctypes.sizeof(alignment_list_t) == 
 assert ctypes.sizeof(ssa_hit_t) == 24 and ctypes.sizeof(ssa_amd_pair_alignment_t) == 56
 assert ctypes.sizeof(ssa_amd_pair_summary_t) == 56
 
+
+class ssa_amd_hits_stats_t(Structure):
+    _fields_ = [("hits", c_uint64), ("gathered", c_uint64), ("fetched", c_uint64), ("upload_bytes", c_uint64),
+                ("gather_ms", c_double)]
+
 # every symbol include/*.h declares (checked by tests/test_abi.py)
 EXPORTS = {
     "libssa_amd.so": ["set_output_mode", "set_simd_compute_mode", "set_chunk_size", "set_thread_count",
@@ -128,7 +133,8 @@ EXPORTS = {
                       "ssa_amd_prune_start_order", "ssa_amd_get_pruned_whole", "ssa_amd_align_hits",
                       "ssa_amd_get_align_hits_stats", "ssa_amd_summarize_pairs_local",
                       "ssa_amd_score_pairs_xdrop", "ssa_amd_align_pairs_xdrop", "ssa_amd_summarize_pairs_xdrop",
-                      "ssa_amd_get_xdrop_dropped", "ssa_amd_search_above", "ssa_amd_merge_above"],
+                      "ssa_amd_get_xdrop_dropped", "ssa_amd_search_above", "ssa_amd_merge_above",
+                      "ssa_amd_summarize_hits", "ssa_amd_get_summarize_hits_stats"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -214,6 +220,8 @@ def load():
         "ssa_amd_summarize_pairs_xdrop": ([c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_size_t, c_void_p], c_int),
         "ssa_amd_get_xdrop_dropped": ([], c_uint64),
+        "ssa_amd_summarize_hits": ([P, c_int, c_void_p, c_size_t, c_void_p], c_int),
+        "ssa_amd_get_summarize_hits_stats": ([POINTER(ssa_amd_hits_stats_t)], None),
         "ssa_amd_map_residues": ([c_char_p, c_size_t, c_char_p, c_size_t], c_size_t),
         "ssa_amd_shard_bounds": ([c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_size_t)], c_int),
     }
@@ -916,6 +924,39 @@ def align_hits(q, algo, hits):
     res = _unpack(al)
     L.free_alignment(al)
     return res
+
+
+def summarize_hits(q, mode, hits):
+    """ssa_amd_summarize_hits: summarize_pairs_local's tuples [(score, (q_begin,
+    q_end, d_begin, d_end), columns, matched, identical, flags)] for hits of
+    the open DB -- tuples (score, db_id[, query_id, db_strand, db_frame]) as
+    search and search_above return them; the d side is the entry as the search
+    scored it.  None when the library refuses the hits."""
+    out = summarize_hits_flat(q, mode, _hit_array(hits), len(hits))
+    if out is None:
+        return None
+    return [(int(o["score"]), tuple(int(x) for x in o["region"]), int(o["columns"]), int(o["matched"]),
+             int(o["identical"]), int(o["flags"])) for o in out]
+
+
+def summarize_hits_flat(q, mode, hit_array, n):
+    """ssa_amd_summarize_hits on the C layout itself: the first n ssa_hit_t of a
+    ctypes array (as _hits / search write them) -> SUMMARY_DTYPE records, or
+    None when the library refuses them."""
+    import numpy as np
+    out = np.zeros(n, np.dtype(SUMMARY_DTYPE))
+    rc = load().ssa_amd_summarize_hits(q, mode, ctypes.addressof(hit_array) if n else None, n,
+                                       out.ctypes.data if n else None)
+    return out if rc == 0 else None
+
+
+def summarize_hits_stats():
+    """ssa_amd_get_summarize_hits_stats: what only the last summarize_hits call
+    has (hits, gathered, fetched, upload_bytes, gather_ms) as a dict; the rest
+    of the call is in align_pairs_stats()."""
+    s = ssa_amd_hits_stats_t()
+    load().ssa_amd_get_summarize_hits_stats(ctypes.byref(s))
+    return {f: getattr(s, f) for f, _ in ssa_amd_hits_stats_t._fields_}
 
 
 def align_hits_stats():

@@ -861,6 +861,14 @@ int ssa_amd_summarize_pairs_xdrop(int mode, int64_t xdrop, const int64_t* band_l
 
 uint64_t ssa_amd_get_xdrop_dropped(void) { return xdrop_dropped(); }
 
+int ssa_amd_summarize_hits(p_query query, int mode, const ssa_hit_t* hits, size_t n, ssa_amd_pair_summary_t* out) {
+    return summarize_hits(query, mode, hits, n, out);
+}
+
+void ssa_amd_get_summarize_hits_stats(ssa_amd_hits_stats_t* out) {
+    if (out) *out = summarize_hits_stats();
+}
+
 size_t ssa_amd_map_residues(const char* ascii, size_t len, char* out, size_t cap) {
     const int st = cfg().symtype;
     const signed char* map = (st == AMINOACID || st == TRANS_QUERY) ? map_aa() : map_nt();
@@ -930,6 +938,7 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "pairs_chunk")) cfg().pairs_chunk = (int)std::max(0L, std::min(value, 1L << 30));
     else if (!strcmp(name, "pairs_host")) cfg().pairs_host = (int)value;
     else if (!strcmp(name, "pairs_gather")) cfg().pairs_gather = (int)value;
+    else if (!strcmp(name, "hits_gather")) cfg().hits_gather = (int)value;
     else if (!strcmp(name, "pairs_pool_mb")) cfg().pairs_pool_mb = (int)std::max(0L, std::min(value, 1L << 20));
     else if (!strcmp(name, "pairs_wave")) cfg().pairs_wave = (int)value;
     else if (!strcmp(name, "align_wave")) cfg().align_wave = (int)value;

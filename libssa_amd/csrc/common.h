@@ -87,6 +87,9 @@ struct Config {
     int pairs_host = 0;                   // 1: every pair of ssa_amd_score_pairs on the exact host path
     int pairs_gather = 1;                 // ssa_amd_score_pairs_indexed: 1 (default) packs on the device from the
                                           // uploaded pools (pairs_gather.hip), 0 packs on the host
+    int hits_gather = 1;                  // ssa_amd_summarize_hits: 1 (default) the hits' DB sides are packed on the
+                                          // device from the packed DB (hits_gather.hip), 0 fetched through the plugin
+                                          // and packed by ssa_amd_summarize_pairs_local
     int pairs_pool_mb = 1024;             // ... and packs on the host when the pools exceed this many MiB
     int pairs_wave = 0;                   // 1: ssa_amd_align_pairs aligns on the wave kernels, one wave per pair
                                           // (align_wave.cpp); 0: one pair per lane (pairs_align.cpp)
@@ -273,6 +276,9 @@ int summarize_pairs_xdrop(int mode, int64_t xdrop, const int64_t* band_lo, const
                           const uint8_t* q_codes, const uint64_t* q_off, const uint8_t* d_codes, const uint64_t* d_off,
                           size_t npairs, ssa_amd_pair_summary_t* out);
 uint64_t xdrop_dropped();
+// hits_summary.cpp: ssa_amd_summarize_hits; it reports through the align statistics and its own
+int summarize_hits(p_query query, int mode, const ssa_hit_t* hits, size_t n, ssa_amd_pair_summary_t* out);
+const ssa_amd_hits_stats_t& summarize_hits_stats();
 void set_pairs_stats(const ssa_amd_pairs_stats_t& s);
 void set_align_pairs_stats(const ssa_amd_align_pairs_stats_t& s);
 

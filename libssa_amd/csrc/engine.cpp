@@ -146,6 +146,7 @@ void DeviceDB::release() {
     generation = ~0ull;
     meta = EntryMeta();
     lane_out.clear();
+    entry_lane.clear();
 }
 
 constexpr size_t kOvfPinned = 4096;      // overflow entries the pinned mirrors hold (more: pageable copies)
@@ -197,6 +198,37 @@ struct Staged {
     std::vector<std::pair<size_t, size_t>> unknown;   // (record, count) with unknown symbols
 };
 
+// The entries of one non-empty nucleotide record (NUCLEOTIDE, TRANS_DB,
+// TRANS_BOTH), in the packer's order: add(codes, len, strand, frame) for each.
+// nt: scratch of the caller; returns the record's unknown symbols.
+template <class Add>
+size_t record_entries(p_seqinfo si, int st, int strands, std::vector<uint8_t>& nt, Add&& add) {
+    const size_t n = si->seqlen;
+    nt.resize(n);
+    const size_t unknown = map_record(si->seq, n, map_nt(), nt.data());
+    if (st == NUCLEOTIDE) {
+        add(nt.data(), n, 0, 0);
+        if (strands & 2) {
+            std::vector<uint8_t> rc(n);
+            revcompl(nt.data(), n, rc.data());
+            add(rc.data(), n, 1, 0);
+        }
+    } else if (strands == BOTH_STRANDS) {
+        for (int s = 0; s < 2; s++)
+            for (int f = 0; f < 3; f++) {
+                auto p = translate(true, nt.data(), n, s, f);
+                add(p.data(), p.size() - 1, s, f);
+            }
+    } else {
+        // reference quirk (db_adapter.c:85-93): strand field = strands
+        for (int f = 0; f < 3; f++) {
+            auto p = translate(true, nt.data(), n, strands - 1, f);
+            add(p.data(), p.size() - 1, strands, f);
+        }
+    }
+    return unknown;
+}
+
 // Records [r0, r1) -> entries, as db_adapter.c:47-110 + 212-239 build them.
 void stage_range(size_t r0, size_t r1, Staged& S) {
     const int st = cfg().symtype, strands = cfg().strands;
@@ -218,31 +250,8 @@ void stage_range(size_t r0, size_t r1, Staged& S) {
             M.residues += len;
         };
         size_t unknown;
-        if (st == NUCLEOTIDE) {
-            nt.resize(n);
-            unknown = map_record(si->seq, n, map_nt(), nt.data());
-            add(nt.data(), n, 0, 0);
-            if (strands & 2) {
-                std::vector<uint8_t> rc(n);
-                revcompl(nt.data(), n, rc.data());
-                add(rc.data(), n, 1, 0);
-            }
-        } else if (st == TRANS_DB || st == TRANS_BOTH) {
-            nt.resize(n);
-            unknown = map_record(si->seq, n, map_nt(), nt.data());
-            if (strands == BOTH_STRANDS) {
-                for (int s = 0; s < 2; s++)
-                    for (int f = 0; f < 3; f++) {
-                        auto p = translate(true, nt.data(), n, s, f);
-                        add(p.data(), p.size() - 1, s, f);
-                    }
-            } else {
-                // reference quirk (db_adapter.c:85-93): strand field = strands
-                for (int f = 0; f < 3; f++) {
-                    auto p = translate(true, nt.data(), n, strands - 1, f);
-                    add(p.data(), p.size() - 1, strands, f);
-                }
-            }
+        if (st == NUCLEOTIDE || st == TRANS_DB || st == TRANS_BOTH) {
+            unknown = record_entries(si, st, strands, nt, add);
         } else {
             const size_t base = S.codes.size();
             S.codes.resize(base + n);
@@ -522,6 +531,7 @@ void upload_pack(DeviceDB& D, HostPack& H, int dev) {
     D.len_sorted.assign(H.lane_len.rbegin() + (H.lane_len.size() - E), H.lane_len.rend());
     D.meta = std::move(H.meta);
     D.lane_out = std::move(H.lane_out);
+    D.entry_lane.clear();                 // entry_lanes() rebuilds it for this pack
     D.code_of = std::move(H.code_of);
     D.alpha = (uint32_t)D.code_of.size();
     D.generation = C.db_generation;
@@ -544,6 +554,43 @@ template <class T>
 bool rd(FILE* f, T* p, size_t n) { return n == 0 || fread(p, sizeof(T), n, f) == n; }
 
 }  // namespace
+
+// One entry's codes exactly as stage_range stages them -- what the search
+// scores: for NUCLEOTIDE strand 1 the reverse complement (fetch_entry_codes
+// keeps the reference aligner's forward copy instead).  False when the open DB
+// has no such entry: no such record, an empty one, or a strand / frame the
+// symbol type and strands do not produce.
+bool staged_entry_codes(uint64_t local_id, int strand, int frame, std::vector<uint8_t>& out) {
+    if (local_id >= ssa_db_get_sequence_count()) return false;
+    p_seqinfo si = ssa_db_get_sequence(local_id);
+    if (!si || si->seqlen == 0) return false;
+    const int st = cfg().symtype;
+    if (st == NUCLEOTIDE || st == TRANS_DB || st == TRANS_BOTH) {
+        bool found = false;
+        std::vector<uint8_t> nt;
+        record_entries(si, st, cfg().strands, nt, [&](const uint8_t* c, size_t len, int s, int f) {
+            if (s != strand || f != frame || found) return;
+            out.assign(c, c + len);
+            found = true;
+        });
+        return found;
+    }
+    if (strand != 0 || frame != 0) return false;
+    out.resize(si->seqlen);
+    map_record(si->seq, si->seqlen, map_aa(), out.data());
+    return true;
+}
+
+// entry -> global lane of the packed DB, the inverse of lane_out: built at the first use after a pack
+// (upload_pack empties it), host only -- d_entry_lane stays what it is
+const std::vector<uint32_t>& entry_lanes(DeviceDB& D) {
+    if (D.entry_lane.size() != D.meta.size()) {
+        D.entry_lane.assign(D.meta.size(), 0xffffffffu);
+        for (size_t l = 0; l < D.lane_out.size(); l++)
+            if (D.lane_out[l] != 0xffffffffu) D.entry_lane[D.lane_out[l]] = (uint32_t)l;
+    }
+    return D.entry_lane;
+}
 
 std::vector<SlotPlan> device_plan() {
     const Config& C = cfg();

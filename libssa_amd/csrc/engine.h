@@ -159,6 +159,7 @@ struct DeviceDB {
     int64_t* d_rscratch = nullptr;        // the int32 re-score tier's multi-pass rows (LongArgs::list)
     size_t rscratch_cap = 0;              // int64 elements
     std::vector<uint32_t> lane_out;       // host copy for overflow mapping
+    std::vector<uint32_t> entry_lane;     // its inverse, entry -> global lane (entry_lanes(); empty: not yet built)
     std::vector<uint32_t> len_sorted;     // entry lengths, ascending
     // residues are stored in a compact alphabet: device code c < alpha stands
     // for residue code code_of[c]; code alpha is the padding column
@@ -203,6 +204,11 @@ void ensure_device_db();                  // every slot of device_plan()
 int save_packed_db(const char* path);     // 0 on success (single device)
 int load_packed_db(const char* path);     // 0 on success; replaces packing from the plugin
 std::vector<uint8_t> fetch_entry_codes(uint64_t local_id, int strand, int frame);
+// One entry's codes as the packer stages them (what the search scores; NUCLEOTIDE strand 1: the reverse
+// complement, where fetch_entry_codes keeps the reference aligner's forward copy); false: no such entry
+bool staged_entry_codes(uint64_t local_id, int strand, int frame, std::vector<uint8_t>& out);
+// entry -> global lane (group * 64 + lane) of D's pack: the inverse of DeviceDB::lane_out, built once per pack
+const std::vector<uint32_t>& entry_lanes(DeviceDB& D);
 
 // Exact scores of every entry for every query view.  Scores live in the
 // pinned int32 buffer (view-major); entries re-scored by the int64 kernel

@@ -219,9 +219,23 @@ uint64_t pair_dir_rows(uint64_t ql, uint64_t dl, int64_t lo, int64_t hi) {
     return (ql + 7) / 8 * blocks;
 }
 
+namespace {
+
 // A wave sweeps, strip by strip, the union of its lanes' in-band columns: order by strip count
 // (longest first), then by the band's position, so that the union is little wider than one lane's.
-uint64_t BandBatch::order(bool align, size_t row_bytes) {
+// Batch: the length source (BandBatch: offsets; BandDescBatch: descriptors), one instantiation each.
+template <class Batch>
+uint64_t order_batch(Batch& B, bool align, size_t row_bytes) {
+    auto& idx = B.idx;
+    auto& groups = B.groups;
+    auto& strips = B.strips;
+    auto& drows = B.drows;
+    auto& gbytes = B.gbytes;
+    const int64_t* lo = B.lo;
+    const int64_t* hi = B.hi;
+    auto nstrips = [&](size_t i) { return B.nstrips(i); };
+    auto qlen = [&](size_t i) { return B.qlen(i); };
+    auto dlen = [&](size_t i) { return B.dlen(i); };
     struct Key {
         uint32_t strips;
         int64_t lo, hi;
@@ -292,7 +306,11 @@ uint64_t BandBatch::order(bool align, size_t row_bytes) {
 // Cuts the chunk that starts at g0 (within the byte budget, at least one
 // group), packs it lane-interleaved into the pinned block and enqueues its
 // upload; sizes every device buffer the kernels of the chunk touch.
-BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const EndsRouting& T) {
+// kResidues false (BandDescBatch): the same block without the residue rows and
+// the lens -- a device-side packer writes those into a buffer of the caller's
+// -- and with the batch's descriptor of every lane behind the bands.
+template <bool kResidues, class Batch>
+BandChunk pack_chunk(Batch& B, size_t g0, bool align, int ends, const EndsRouting& T) {
     BandedDevice& P = g_dev;
     const Config& C = cfg();
     const size_t ngroups = B.groups.size(), npd = B.idx.size();
@@ -329,15 +347,19 @@ BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const
     K.p0 = g0 * 64;
     K.p1 = std::min(npd, g1 * 64);
     K.drow = drow;
+    K.qrow = qrow;
+    K.trow = trow;
     // the upload block: matrix, groups, strips, lens, bands, lanes (the align call), query and target residues
+    // (without residues: matrix, groups, strips, bands, descriptors)
     const size_t o_groups = pairs_align_up(sizeof T.mt);
     const size_t o_strips = o_groups + pairs_align_up(K.ng * sizeof(BandGroup));
     const size_t o_lens = o_strips + pairs_align_up((size_t)srow * sizeof(BandStrip));
-    const size_t o_band = o_lens + pairs_align_up(K.nl * sizeof(uint2));
+    const size_t o_band = o_lens + (kResidues ? pairs_align_up(K.nl * sizeof(uint2)) : 0);
     const size_t o_lanes = o_band + pairs_align_up(K.nl * sizeof(int2));
     const size_t o_q = o_lanes + (align ? pairs_align_up(K.nl * sizeof(AlignLane)) : 0);
-    const size_t o_t = o_q + (size_t)qrow * 256;
-    const size_t up_bytes = o_t + (size_t)trow * 256;
+    const size_t o_t = o_q + (kResidues ? (size_t)qrow * 256 : pairs_align_up(K.nl * sizeof(HitDesc)));
+    const size_t up_bytes = kResidues ? o_t + (size_t)trow * 256 : o_t;
+    K.up_bytes = up_bytes;
     P.up.need(up_bytes, true, "pairs_banded residues");
     P.bnd.need((size_t)brow * 512, false, "pairs_banded boundary buffer");
     P.out.need(K.nl * (sizeof(int2) + sizeof(uint32_t)), true, "pairs_banded results");
@@ -346,32 +368,43 @@ BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const
     memcpy(P.up.h, T.mt, sizeof T.mt);
     memcpy(P.up.h + o_groups, cg.data(), K.ng * sizeof(BandGroup));
     memcpy(P.up.h + o_strips, B.strips.data() + s_first, (size_t)srow * sizeof(BandStrip));
-    uint2* h_lens = (uint2*)(P.up.h + o_lens);
     int2* h_band = (int2*)(P.up.h + o_band);
-    parallel_ranges(K.ng, 1, [&](size_t b, size_t e) {
-        for (size_t g = g0 + b; g < g0 + e; g++) {
-            const BandGroup& G = cg[g - g0];
-            uint8_t* tq = P.up.h + o_q + (size_t)G.q_row * 256;
-            uint8_t* tt = P.up.h + o_t + (size_t)G.t_row * 256;
-            memset(tq, (int)kPairsPad, (size_t)G.nstrips * 2 * 256);
-            memset(tt, (int)kPairsPad, (size_t)G.ncb * 256);
-            for (size_t l = 0; l < 64; l++) {
-                const size_t p = g * 64 + l;
-                uint2& L = h_lens[(g - g0) * 64 + l];
-                int2& W = h_band[(g - g0) * 64 + l];
-                if (p >= npd) {
-                    L = make_uint2(0, 0);
-                    W = make_int2(0, 0);
-                    continue;
+    if constexpr (kResidues) {
+        uint2* h_lens = (uint2*)(P.up.h + o_lens);
+        parallel_ranges(K.ng, 1, [&](size_t b, size_t e) {
+            for (size_t g = g0 + b; g < g0 + e; g++) {
+                const BandGroup& G = cg[g - g0];
+                uint8_t* tq = P.up.h + o_q + (size_t)G.q_row * 256;
+                uint8_t* tt = P.up.h + o_t + (size_t)G.t_row * 256;
+                memset(tq, (int)kPairsPad, (size_t)G.nstrips * 2 * 256);
+                memset(tt, (int)kPairsPad, (size_t)G.ncb * 256);
+                for (size_t l = 0; l < 64; l++) {
+                    const size_t p = g * 64 + l;
+                    uint2& L = h_lens[(g - g0) * 64 + l];
+                    int2& W = h_band[(g - g0) * 64 + l];
+                    if (p >= npd) {
+                        L = make_uint2(0, 0);
+                        W = make_int2(0, 0);
+                        continue;
+                    }
+                    const uint32_t i = B.idx[p];
+                    L = make_uint2(B.qlen(i), B.dlen(i));
+                    W = make_int2((int)B.lo[i], (int)B.hi[i]);
+                    interleave(tq + l * 4, B.qc + B.qoff[i], B.qlen(i));
+                    interleave(tt + l * 4, B.dc + B.doff[i], B.dlen(i));
                 }
-                const uint32_t i = B.idx[p];
-                L = make_uint2(B.qlen(i), B.dlen(i));
-                W = make_int2((int)B.lo[i], (int)B.hi[i]);
-                interleave(tq + l * 4, B.qc + B.qoff[i], B.qlen(i));
-                interleave(tt + l * 4, B.dc + B.doff[i], B.dlen(i));
             }
+        });
+    } else {
+        // (an unused lane's descriptor is all zero)
+        HitDesc* h_desc = (HitDesc*)(P.up.h + o_q);
+        for (size_t l = 0; l < K.nl; l++) {
+            const size_t p = K.p0 + l;
+            h_band[l] = p < npd ? make_int2((int)B.lo[B.idx[p]], (int)B.hi[B.idx[p]]) : make_int2(0, 0);
+            h_desc[l] = p < npd ? B.desc[B.idx[p]] : HitDesc{0, 0, 0, 0};
         }
-    });
+        K.desc = (const HitDesc*)(P.up.d + o_q);
+    }
     if (align) {
         // the walk's lanes: a run slot of qlen + dlen each (a walk makes at most that many steps)
         K.lanes = (AlignLane*)(P.up.h + o_lanes);
@@ -392,11 +425,11 @@ BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const
     A.mt = (const int8_t*)P.up.d;
     A.groups = (const BandGroup*)(P.up.d + o_groups);
     A.strips = (const BandStrip*)(P.up.d + o_strips);
-    A.lens = (const uint2*)(P.up.d + o_lens);
+    A.lens = kResidues ? (const uint2*)(P.up.d + o_lens) : nullptr;
     A.band = (const int2*)(P.up.d + o_band);
     A.lanes = align ? (const AlignLane*)(P.up.d + o_lanes) : nullptr;
-    A.qres = (const uint32_t*)(P.up.d + o_q);
-    A.tres = (const uint32_t*)(P.up.d + o_t);
+    A.qres = kResidues ? (const uint32_t*)(P.up.d + o_q) : nullptr;
+    A.tres = kResidues ? (const uint32_t*)(P.up.d + o_t) : nullptr;
     A.bnd = (int2*)P.bnd.d;
     A.dir = align ? (uint4*)P.dir.d : nullptr;
     A.runs = align ? (uint32_t*)P.runs.d : nullptr;
@@ -407,6 +440,19 @@ BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const
     A.ends = ends;
     A.ngroups = (uint32_t)K.ng;
     return K;
+}
+
+}  // namespace
+
+uint64_t BandBatch::order(bool align, size_t row_bytes) { return order_batch(*this, align, row_bytes); }
+uint64_t BandDescBatch::order(bool align, size_t row_bytes) { return order_batch(*this, align, row_bytes); }
+
+BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const EndsRouting& T) {
+    return pack_chunk<true>(B, g0, align, ends, T);
+}
+
+BandChunk banded_pack_chunk_tables(BandDescBatch& B, size_t g0, int ends, const EndsRouting& T) {
+    return pack_chunk<false>(B, g0, false, ends, T);
 }
 
 void banded_host_align(int ends, const uint8_t* q, size_t ql, const uint8_t* d, size_t dl, int64_t lo, int64_t hi,

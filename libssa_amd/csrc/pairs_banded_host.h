@@ -1,11 +1,13 @@
 // pairs_banded_host.h -- the host side of the banded pair calls that the local
-// pair calls share (defined in pairs_banded.cpp; used by pairs_local.cpp, pairs_summary.cpp and pairs_xdrop.cpp): the
+// pair calls share (defined in pairs_banded.cpp; used by pairs_local.cpp, pairs_summary.cpp, pairs_xdrop.cpp and
+// hits_summary.cpp): the
 // band's clamp and validity rule, the batch ordered by shape and band with its
 // BandStrip ranges, the chunk packer and the device buffers it fills.  Host
 // code only.
 #pragma once
 #include <vector>
 
+#include "hits_gather.h"
 #include "pairs_banded.h"
 #include "pairs_host.h"
 #include "pairs_summary.h"
@@ -61,12 +63,34 @@ struct BandBatch {
     uint64_t order(bool align, size_t row_bytes = kBandDirRowBytes);
 };
 
+// The same batch for pairs whose residues are not on the host (hits_summary.cpp): the length source is one
+// descriptor per pair, which is also what a chunk uploads for the pair's lane.  order() is BandBatch's, and
+// so are the groups, the strips and the chunks cut from them.
+struct BandDescBatch {
+    const HitDesc* desc;                // by input index
+    const int64_t* lo;                  // clamped, by input index
+    const int64_t* hi;
+    std::vector<uint32_t> idx;
+    std::vector<BandGroup> groups;
+    std::vector<BandStrip> strips;
+    std::vector<uint64_t> drows;
+    std::vector<size_t> gbytes;
+
+    uint32_t qlen(size_t i) const { return desc[i].qlen; }
+    uint32_t dlen(size_t i) const { return desc[i].dlen; }
+    uint32_t nstrips(size_t i) const { return (qlen(i) + kPairsRows - 1) / kPairsRows; }
+    uint64_t order(bool align, size_t row_bytes = kBandDirRowBytes);
+};
+
 // One chunk: groups [g0, g1) laid out in the upload block, packed and uploaded.
 struct BandChunk {
     size_t g0, g1, ng, nl, p0, p1;
     uint64_t drow = 0;                  // the align call: 64-lane rows of direction bits
     uint64_t nruns = 0;                 //   and run slots
     AlignLane* lanes = nullptr;         //   the host copy of the lanes
+    uint64_t qrow = 0, trow = 0;        // 64-lane dword rows of qres and tres
+    size_t up_bytes = 0;                // bytes of the upload block
+    const HitDesc* desc = nullptr;      // banded_pack_chunk_tables: the lanes' descriptors on the device
     BandedArgs A{};
 };
 
@@ -74,6 +98,10 @@ struct BandChunk {
 // group), packs it lane-interleaved into the pinned block and enqueues its
 // upload; sizes every device buffer banded_kernel and banded_walk_kernel touch.
 BandChunk banded_pack_chunk(BandBatch& B, size_t g0, bool align, int ends, const EndsRouting& T);
+// The score call's chunk without the residue rows and the lens: the upload block holds the matrix, the
+// groups, the strips, the bands and one descriptor per lane (K.desc); A.lens, A.qres and A.tres are left
+// NULL for the caller, whose device-side packer writes K.nl lens, K.qrow and K.trow rows.
+BandChunk banded_pack_chunk_tables(BandDescBatch& B, size_t g0, int ends, const EndsRouting& T);
 
 // ------------------------------------ what the summary call shares (pairs_summary.cpp)
 // One pair through the host align routine of the banded calls (pairs_banded.cpp; ends: the mask) or of the
@@ -98,6 +126,8 @@ bool xdrop_host_align(int mode, const uint8_t* q, size_t ql, const uint8_t* d, s
                       int64_t xdrop, ssa_amd_pair_alignment_t& o, char* text, bool& dropped);
 // pairs_summary.cpp: the chunk's summary buffers (SummaryArgs over K.A; *h_sum: the pinned twin of sum)
 SummaryArgs summary_chunk_args(const BandBatch& B, const BandChunk& K, int dev_id, const uint2** h_sum);
+SummaryArgs summary_chunk_args(const std::vector<BandGroup>& groups, const BandChunk& K, int dev_id,
+                               const uint2** h_sum);
 // ... one device lane's record from its end cell and its words; true for the empty alignment under a local bit
 bool summary_record(bool local, int2 end, uint2 words, ssa_amd_pair_summary_t& o);
 // ... columns, matched and identical of a CIGAR text walked from (region[0], region[2]), added to o

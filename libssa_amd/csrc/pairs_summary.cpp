@@ -86,7 +86,7 @@ struct SummaryDevice {
     PairsBuf rows, sum;
 } g_dev;
 
-SummaryArgs summary_args(const BandBatch& B, const BandChunk& K, int dev_id) {
+SummaryArgs summary_args(const std::vector<BandGroup>& groups, const BandChunk& K, int dev_id) {
     SummaryDevice& P = g_dev;
     if (P.device != dev_id) {
         P.rows.release();
@@ -95,7 +95,7 @@ SummaryArgs summary_args(const BandBatch& B, const BandChunk& K, int dev_id) {
     }
     // as many 64-lane rows as the chunk's bnd has: four per column block of every group
     uint64_t brow = 0;
-    for (size_t g = K.g0; g < K.g1; g++) brow += (uint64_t)B.groups[g].ncb * 4;
+    for (size_t g = K.g0; g < K.g1; g++) brow += (uint64_t)groups[g].ncb * 4;
     P.rows.need(std::max<size_t>((size_t)brow, 1) * 64 * sizeof(uint4), false, "pairs_summary row buffer");
     P.sum.need(K.nl * sizeof(uint2), true, "pairs_summary results");
     SummaryArgs A;
@@ -108,10 +108,15 @@ SummaryArgs summary_args(const BandBatch& B, const BandChunk& K, int dev_id) {
 }  // namespace
 
 // ---- shared with pairs_xdrop.cpp (pairs_banded_host.h)
-SummaryArgs summary_chunk_args(const BandBatch& B, const BandChunk& K, int dev_id, const uint2** h_sum) {
-    const SummaryArgs A = summary_args(B, K, dev_id);
+SummaryArgs summary_chunk_args(const std::vector<BandGroup>& groups, const BandChunk& K, int dev_id,
+                               const uint2** h_sum) {
+    const SummaryArgs A = summary_args(groups, K, dev_id);
     *h_sum = (const uint2*)g_dev.sum.h;
     return A;
+}
+
+SummaryArgs summary_chunk_args(const BandBatch& B, const BandChunk& K, int dev_id, const uint2** h_sum) {
+    return summary_chunk_args(B.groups, K, dev_id, h_sum);
 }
 
 bool summary_record(bool local, int2 end, uint2 words, ssa_amd_pair_summary_t& o) {
@@ -182,7 +187,7 @@ int summarize_pairs_local(int mode, const int64_t* band_lo, const int64_t* band_
         for (size_t g0 = 0; g0 < B.groups.size();) {
             const double tc0 = now_ms();
             const BandChunk K = banded_pack_chunk(B, g0, false, mode & 15, T);
-            const SummaryArgs A = summary_args(B, K, T.dev_id);
+            const SummaryArgs A = summary_args(B.groups, K, T.dev_id);
             S.pack_ms += now_ms() - tc0;
             // ---- the end cells, then the sweep with the words, captured at out's end cells
             check(hipEventRecord(P.ev[0], T.stream), "hipEventRecord");
