@@ -189,6 +189,10 @@ void ssa_amd_get_stats( ssa_amd_stats_t * out );
  * (option "prune_len"); their later units return at once and are not counted in
  * pruned_units.  A batch reports the sum. */
 uint32_t ssa_amd_get_pruned_whole( void );
+/* ... and the entries of a pruned search that were scored exactly, one wave
+ * each, at the first part boundary instead of in place (option
+ * "prune_promote").  A batch reports the sum. */
+uint32_t ssa_amd_get_promoted_lanes( void );
 /* Tuning knobs (results never change, only which kernel computes them):
  *   "strip_np" 8|16|32   int16 strip kernels: packed rows per strip
  *   "pair_np" 0|16|24|32|36|40  pair kernel main strip of 2 x pair_np rows; 0 (default):
@@ -260,6 +264,11 @@ uint32_t ssa_amd_get_pruned_whole( void );
  *                        its remaining parts itself, at once, when its best entry so far has reached
  *                        N % (default 25) of the most the query rows so far can score; 0: never.
  *                        Changes the schedule only, never a score (stats inplace_units)
+ *   "prune_promote" 1|0  1 (default): a work unit that would run its remaining parts itself scores its
+ *                        promising entries (up to 8 per 64, queries of up to 512 rows) exactly at once
+ *                        instead, one wave per entry, so the k-th best score is known early, and leaves
+ *                        its later parts to the ordinary skip (ssa_amd_get_promoted_lanes); 0: in place.
+ *                        Changes the schedule only, never a score
  *   "prune_len" 1|0      1 (default): a pruned search skips a whole work unit, before its first row, when
  *                        none of its entries is long enough to reach the current k-th best score
  *                        (ssa_amd_get_pruned_whole); hits are identical

@@ -130,7 +130,8 @@ EXPORTS = {
                       "ssa_amd_score_pairs_ends", "ssa_amd_align_pairs_ends",
                       "ssa_amd_score_pairs_banded", "ssa_amd_align_pairs_banded",
                       "ssa_amd_score_pairs_local", "ssa_amd_align_pairs_local", "ssa_amd_score_pairs_indexed",
-                      "ssa_amd_prune_start_order", "ssa_amd_get_pruned_whole", "ssa_amd_align_hits",
+                      "ssa_amd_prune_start_order", "ssa_amd_get_pruned_whole", "ssa_amd_get_promoted_lanes",
+                      "ssa_amd_align_hits",
                       "ssa_amd_get_align_hits_stats", "ssa_amd_summarize_pairs_local",
                       "ssa_amd_score_pairs_xdrop", "ssa_amd_align_pairs_xdrop", "ssa_amd_summarize_pairs_xdrop",
                       "ssa_amd_get_xdrop_dropped", "ssa_amd_search_above", "ssa_amd_merge_above",
@@ -187,6 +188,7 @@ def load():
                                 POINTER(ssa_hit_t)], c_size_t),
         "ssa_amd_get_timeline": ([c_void_p, c_size_t], c_size_t),
         "ssa_amd_get_pruned_whole": ([], ctypes.c_uint32),
+        "ssa_amd_get_promoted_lanes": ([], ctypes.c_uint32),
         "ssa_amd_prune_start_order": ([c_void_p, c_size_t, c_size_t, ctypes.c_uint, ctypes.c_uint, c_void_p, c_size_t],
                                       c_size_t),
         "ssa_amd_dist_available": ([], c_int), "ssa_amd_dist_init_fake": ([c_int, c_int, c_int], c_int),
@@ -349,6 +351,8 @@ def stats():
     load().ssa_amd_get_stats(ctypes.byref(s))
     d = {f: getattr(s, f) for f, _ in ssa_amd_stats_t._fields_}
     d["pruned_whole"] = int(load().ssa_amd_get_pruned_whole())    # (beside the struct, whose layout is kept)
+    # (an older build under A/B measurement has no such call)
+    d["promoted_lanes"] = int(load().ssa_amd_get_promoted_lanes()) if hasattr(load(), "ssa_amd_get_promoted_lanes") else 0
     d["kernel"] = d["kernel"].decode()
     d["long_kernel"] = d["long_kernel"].decode()
     n = d["slots"]

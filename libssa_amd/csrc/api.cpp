@@ -31,6 +31,11 @@ uint32_t& pruned_whole_stat() {
     static uint32_t n = 0;
     return n;
 }
+// ... and its entries scored exactly at the first cut (ssa_amd_get_promoted_lanes)
+uint32_t& promoted_lanes_stat() {
+    static uint32_t n = 0;
+    return n;
+}
 
 // The environment's device list as the search uses it: its first
 // set_thread_count() devices -- the reference's thread count is its number of
@@ -272,6 +277,7 @@ void publish_stats(const std::vector<SearchScores>& sc, const std::vector<SlotPl
     S.rare_merged = S.rare_rescored = 0;
     S.part_units = S.pruned_units = S.inplace_units = S.pruned_first = 0;
     pruned_whole_stat() = 0;
+    promoted_lanes_stat() = 0;
     for (const SearchScores& x : sc) {
         S.part_retries += x.part_retries;
         S.part_units += x.part_units;
@@ -279,6 +285,7 @@ void publish_stats(const std::vector<SearchScores>& sc, const std::vector<SlotPl
         S.inplace_units += x.inplace_units;
         S.pruned_first += x.pruned_first;
         pruned_whole_stat() += x.pruned_whole;
+        promoted_lanes_stat() += x.promoted_lanes;
         S.rare_merged = std::max(S.rare_merged, x.rare_merged);
         S.rare_rescored += x.rare_rescored;
     }
@@ -718,6 +725,7 @@ size_t ssa_amd_prune_start_order(const uint32_t* ncols, size_t ngroups, size_t q
 }
 
 uint32_t ssa_amd_get_pruned_whole(void) { return pruned_whole_stat(); }
+uint32_t ssa_amd_get_promoted_lanes(void) { return promoted_lanes_stat(); }
 
 void ssa_amd_get_stats(ssa_amd_stats_t* out) {
     if (!out) return;
@@ -921,6 +929,7 @@ void ssa_amd_set_option(const char* name, long value) {
     else if (!strcmp(name, "topk_prune")) cfg().topk_prune = (int)value;
     else if (!strcmp(name, "prune_inplace_pct")) cfg().prune_inplace_pct = (int)std::min(100L, std::max(0L, value));
     else if (!strcmp(name, "prune_len")) cfg().prune_len = (int)value;
+    else if (!strcmp(name, "prune_promote")) cfg().prune_promote = (int)value;
     else if (!strcmp(name, "prune_order")) cfg().prune_order = (int)value;
     else if (!strcmp(name, "prune_order_pct")) cfg().prune_order_pct = (int)std::min(400L, std::max(0L, value));
     else if (!strcmp(name, "sync_spin")) cfg().sync_spin = (int)value;
@@ -994,7 +1003,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         std::iota(ord.begin(), ord.end(), (size_t)0);
         std::stable_sort(ord.begin(), ord.end(),
                          [&](size_t x, size_t y) { return qviews[x][0].len < qviews[y][0].len; });
-        uint32_t launches = 0, retries = 0, punits = 0, pruned = 0, inplace = 0, pfirst = 0, pwhole = 0;
+        uint32_t launches = 0, retries = 0, punits = 0, pruned = 0, inplace = 0, pfirst = 0, pwhole = 0, ppromo = 0;
         uint64_t ncand = 0;
         for (size_t b0 = 0; b0 < nq; b0 += kMaxBatchPipe) {
             const size_t b1 = std::min(nq, b0 + kMaxBatchPipe);
@@ -1013,6 +1022,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
                 inplace += stats().inplace_units;
                 pfirst += stats().pruned_first;
                 pwhole += pruned_whole_stat();
+                ppromo += promoted_lanes_stat();
                 ncand += stats().filter_candidates;
                 launches++;
                 const size_t n = std::min(hitcount, R.hits.size());
@@ -1058,6 +1068,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         S.inplace_units = inplace;
         S.pruned_first = pfirst;
         pruned_whole_stat() = pwhole;
+        promoted_lanes_stat() = ppromo;
         S.filter_candidates = ncand;
         S.search_ms = now_ms() - t0;
         S.total_searches = before.total_searches + nq;
@@ -1065,7 +1076,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         S.total_search_ms = before.total_search_ms + S.search_ms;
         return total;
     }
-    uint32_t retries = 0, launches = 0, punits = 0, pruned = 0, inplace = 0, pfirst = 0, pwhole = 0;
+    uint32_t retries = 0, launches = 0, punits = 0, pruned = 0, inplace = 0, pfirst = 0, pwhole = 0, ppromo = 0;
     uint64_t ncand = 0;
     for (size_t i = 0; i < nq; i++) {
         test_configuration(queries[i]);
@@ -1079,6 +1090,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
         inplace += stats().inplace_units;
         pfirst += stats().pruned_first;
         pwhole += pruned_whole_stat();
+        ppromo += promoted_lanes_stat();
         ncand += stats().filter_candidates;
         launches += stats().kernel_launches;
         const size_t n = std::min(hitcount, R.hits.size());
@@ -1100,6 +1112,7 @@ size_t ssa_amd_search_batch(const p_query* queries, size_t nq, int algo, size_t 
     S.inplace_units = inplace;
     S.pruned_first = pfirst;
     pruned_whole_stat() = pwhole;
+    promoted_lanes_stat() = ppromo;
     S.filter_candidates = ncand;
     S.kernel_launches = launches;
     S.search_ms = now_ms() - t0;

@@ -105,6 +105,9 @@ struct Config {
                                           // most; 0: never (every later part as a work unit of its own)
     int prune_len = 1;                    // a pruned search skips a whole work unit none of whose entries is long
                                           // enough to reach the threshold (kernels.h kPruneLen; stats pruned_whole)
+    int prune_promote = 1;                // a pruned search's part-0 unit that would finish in place scores its
+                                          // promising entries exactly at once, one wave per entry, and defers its
+                                          // later parts (kernels.h kPruneMask; stats promoted_lanes); 0: in place
     int prune_order = 1;                  // a pruned search starts the units whose entry lengths lie near the
                                           // query's alternately with the longest ones (engine.cpp prune_start_order);
                                           // only with prune_len

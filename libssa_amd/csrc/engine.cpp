@@ -79,7 +79,7 @@ void DeviceDB::release() {
     dfree(d_smax);
     d_part = d_smax = nullptr;
     part_cap = smax_cap = 0;
-    part_quads = part_rows = 0;
+    part_quads = part_rows = part_maskq = 0;
     part_order_key = part_order_key2 = ~0ull;
     dfree(d_rowbuf_q);
     d_rowbuf_q = nullptr;
@@ -1494,7 +1494,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     out.cells = 0;
     out.cand.clear();
     out.dev_o8 = out.dev_o16 = 0;
-    out.part_units = out.pruned_units = out.inplace_units = out.pruned_first = out.pruned_whole = 0;
+    out.part_units = out.pruned_units = out.inplace_units = out.pruned_first = out.pruned_whole = out.promoted_lanes = 0;
     // the reference's overflow counters (counters.hip): per (view, entry)
     // flags, summed on the device after the last view -- only when someone
     // observes them (m_run prints them at OUTPUT_INFO, manager.c:157-160;
@@ -2331,8 +2331,13 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     // (the start order only with the skip: what it buys is a final tau before
                     // the short units take their tickets; alone it measured slower than longest first)
                     const bool want_len = want_prune && len_want, want_ord = want_len && C.prune_order;
+                    // promotion (kernels.h kPruneMask): the query within the
+                    // wave scorer's rows, its profile within the LDS the pair
+                    // table leaves behind; else such units finish in place
+                    const bool want_promo = want_prune && C.prune_promote && main_strips > 0 && m <= 64u * kPromoteRL && A > 0 &&
+                                            promote_lds_bytes(A) <= pair_lds;
                     if (D.part_cap < pl_quads * nqf || (want_ord && D.part_quads < pl_quads) ||
-                        (want_len && D.part_rows < m + 1)) {
+                        (want_len && D.part_rows < m + 1) || (want_promo && D.part_maskq < pl_quads)) {
                         // the pruning block, then per quad (and query) its flag
                         // and bound (kernels.h kPrune*), then a pruned search's
                         // start order and length bounds
@@ -2340,7 +2345,8 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                         const size_t cap = std::max(D.part_cap, pl_quads * nqf);
                         const size_t quads = std::max<size_t>(D.part_quads, want_ord ? pl_quads : 0);
                         const size_t rows = std::max<size_t>(D.part_rows, want_len ? m + 1 + 256 : 0);
-                        const size_t bytes = ((size_t)kPruneWords + cap * 2 + quads + rows) * 4;
+                        const size_t maskq = std::max<size_t>(D.part_maskq, want_promo ? pl_quads : 0);
+                        const size_t bytes = ((size_t)kPruneWords + cap * 2 + quads + rows + maskq * 2 * kPairWaves) * 4;
                         dfree(D.d_part);
                         check(hipMalloc((void**)&D.d_part, bytes), "strip parts");
                         check(hipMemsetAsync(D.d_part, 0, bytes, st), "memset");
@@ -2349,6 +2355,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                         D.part_cap = cap;
                         D.part_quads = quads;
                         D.part_rows = rows;
+                        D.part_maskq = maskq;
                         D.part_order_key = D.part_order_key2 = ~0ull;
                     }
                     if (want_prune) {
@@ -2382,6 +2389,10 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                         }
                     }
                     ta.prune_blk = D.d_part;
+                    if (want_promo) {
+                        ta.prune_mask = (uint32_t)(2 * D.part_cap + D.part_quads + D.part_rows);
+                        ta.prune_mask_n = (uint32_t)(pl_quads * 2 * kPairWaves);
+                    }
                     if (want_prune) {
                         // rem: what the query rows below a part's last one can
                         // add at most, on the codes the kernel scores with
@@ -2947,6 +2958,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 out.inplace_units = D.h_fbuf[5];
                 out.pruned_first = D.h_fbuf[6];
                 out.pruned_whole = D.h_fbuf[7];
+                out.promoted_lanes = D.h_fbuf[8];
             }
             if (nc > D.cand_first) {
                 more.resize(nc);

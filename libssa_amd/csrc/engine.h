@@ -126,6 +126,8 @@ struct DeviceDB {
     // part-0 ticket; kept while its key -- split groups, query rows, window --
     // stays), then its length bounds (kernels.h kPruneOrd, kPruneLen)
     size_t part_quads = 0, part_rows = 0; // what the allocation was sized for
+    // ... and behind those the promoted-lane masks, eight words per quad (kernels.h kPruneMask)
+    size_t part_maskq = 0;
     uint64_t part_order_key = ~0ull, part_order_key2 = ~0ull;
     uint32_t part_epoch = 0;              // the last pair launch's handoff flag value (StripArgs::part_epoch)
     // the long-entry dispatch gate (d_cnt's gate word) is never cleared per
@@ -243,6 +245,7 @@ struct SearchScores {
     // ... the units that ran their remaining parts in place, and the skipped ones of the first part boundary
     uint32_t inplace_units = 0, pruned_first = 0;
     uint32_t pruned_whole = 0;           // units skipped before their first part (no entry long enough)
+    uint32_t promoted_lanes = 0;         // entries scored exactly at the first cut (option "prune_promote")
     int64_t get(size_t v, size_t e) const {
         const int32_t x = s32[v * entries + e];
         if (x != INT32_MIN) return x;

@@ -173,15 +173,40 @@ struct StripArgs {
 // quad's entries can still score below its last row i_b: max over lanes of
 // max_j H(i_b, j), plus rem.  A later part whose bound is below tau writes its
 // lanes' maxima so far as their scores and returns.
+//   mask, promoted, query, matrix: promotion (option "prune_promote").  A part-0
+//     unit that would finish in place scores its promising lanes (maximum >=
+//     prom[0]) exactly instead, one wave per entry against the whole query
+//     (promote_wave.h), offers those final scores to list 2 at once and defers
+//     its later parts as an ordinary unit does, with the bound of its other
+//     lanes.  mask: the dword offset from part_done of the promoted-lane masks,
+//     a word pair per wave of every quad (0: promotion off), zeroed per search
+//     by the tables kernel, which also leaves its own query and matrix pointers
+//     (8 bytes each) for the scorer; promoted: the lanes promoted.  A skipped
+//     later part leaves a promoted lane's score alone, and a later part that
+//     runs does not offer it to list 2 again.
 constexpr uint32_t kPruneLock = 0, kPruneTau = 1, kPruneCount = 2, kPruneK = 3, kPruneRem = 4, kPruneLock2 = 6,
                    kPruneInplace = 7, kPruneFirst = 8, kPruneProm = 9, kPruneCut = 11, kPruneInplaceWaves = 13,
-                   kPruneInplaceDone = 14, kPruneWhole = 15, kPruneLen = 16, kPruneOrd = 17,
+                   kPruneInplaceDone = 14, kPruneWhole = 15, kPruneLen = 16, kPruneOrd = 17, kPruneMask = 18,
+                   kPrunePromoted = 19, kPruneQuery = 20, kPruneMatrix = 22,
                    kPruneList = 24,
                    kPruneList2 = kPruneList + 64, kPruneWords = kPruneList2 + 64;
 // bound values above every score: never skip (a lane the part-0 maximum leaves
 // undecided) / an earlier part of the quad was skipped / the earlier part's
 // workgroup finishes the quad in place (its later units return at once)
 constexpr uint32_t kBoundNever = 0xffffffffu, kBoundSkipped = 0xfffffffeu, kBoundInplace = 0xfffffffdu;
+// Promotion (promote_wave.h): query rows per lane of the scorer (queries of up
+// to 64 x that many rows), the most lanes one wave may promote (more: the unit
+// finishes in place), the longest entry scored that way, and the exact score
+// from which a lane is left to the pair kernel's own path (the 16-bit
+// patterns' range ends there: the unit finishes in place and the lane's
+// result, re-score list included, is what it always was).  In the workgroup's
+// LDS, which the pair table no longer needs: the work list (up to
+// kPairWaves * kPromoteCap items of 4 dwords: lane, length, block, score) from
+// dword kPromoteItems, the profile from dword kPromoteProf.
+constexpr int kPromoteRL = 8;
+constexpr uint32_t kPromoteCap = 8, kPromoteCols = 4096, kPromoteScoreMax = 32767 - kF16Floor;
+constexpr uint32_t kPromoteItems = 64, kPromoteProf = kPromoteItems + 4 * kPairWaves * kPromoteCap;
+constexpr size_t promote_lds_bytes(uint32_t alpha) { return (size_t)kPromoteProf * 4 + (size_t)alpha * 64 * kPromoteRL * 2; }
 
 // Long DB entries (long_kernel): the query rows split over the lanes of W
 // waves (RL consecutive rows per lane, passes of W*64*RL rows), DB columns
@@ -326,7 +351,8 @@ struct FilterArgs {
     uint32_t epoch;
     // single view: the pair kernel's skipped-unit count (kPruneCount),
     // copied into counters[4] like status, with kPruneInplace and kPruneFirst
-    // of the same block into counters[5] and [6], kPruneWhole into [7]; null: none
+    // of the same block into counters[5] and [6], kPruneWhole into [7], kPrunePromoted
+    // into [8]; null: none
     const uint32_t* pruned;
 };
 constexpr int kFilterSeqWord = 15;    // header word that carries FilterArgs::host_seq
@@ -490,6 +516,10 @@ struct TableArgs {
     // prune_lenmax[0 .. prune_len_n) to prune_blk + kPruneWords + prune_len
     uint32_t prune_len, prune_ord, prune_len_n;
     const uint32_t* prune_lenmax;
+    // kPruneMask as it stands (0: no promotion); the kernel's blocks zero the
+    // prune_mask_n mask words at prune_blk + kPruneWords + prune_mask, and
+    // block 0 leaves `query` and `matrix` at kPruneQuery / kPruneMatrix
+    uint32_t prune_mask, prune_mask_n;
 };
 hipError_t launch_pair_tables(const TableArgs& a, hipStream_t st);
 // dst (device) <- src (pinned host), bytes a multiple of 4: a kernel on st

@@ -767,6 +767,7 @@ __global__ void __launch_bounds__(256) filter_select(const FilterArgs a0) {
         a.counters[4] = *a.pruned;
         a.counters[5] = a.pruned[kPruneInplace - kPruneCount];
         a.counters[6] = a.pruned[kPruneFirst - kPruneCount], a.counters[7] = a.pruned[kPruneWhole - kPruneCount];
+        a.counters[8] = a.pruned[kPrunePromoted - kPruneCount];
     }
     const uint32_t e0 = tid * kSelectPer;
     if (e0 < a.n) {
@@ -977,6 +978,7 @@ __global__ void __launch_bounds__(256) filter_onepass(const FilterArgs a0) {
             a.counters[4] = *a.pruned;
             a.counters[5] = a.pruned[kPruneInplace - kPruneCount];
             a.counters[6] = a.pruned[kPruneFirst - kPruneCount], a.counters[7] = a.pruned[kPruneWhole - kPruneCount];
+            a.counters[8] = a.pruned[kPrunePromoted - kPruneCount];
         }
     }
 #pragma unroll
@@ -1057,8 +1059,16 @@ __global__ void __launch_bounds__(256) pair_tables_kernel(const TableArgs a) {
                          : t == kPruneCut || t == kPruneCut + 1 ? a.prune_cut[t - kPruneCut]
                          : t == kPruneLen ? a.prune_len
                          : t == kPruneOrd ? a.prune_ord
-                                          : 0u;
+                         : t == kPruneMask ? a.prune_mask
+                         : t == kPruneQuery ? (uint32_t)(uintptr_t)a.query
+                         : t == kPruneQuery + 1 ? (uint32_t)((uintptr_t)a.query >> 32)
+                         : t == kPruneMatrix ? (uint32_t)(uintptr_t)a.matrix
+                         : t == kPruneMatrix + 1 ? (uint32_t)((uintptr_t)a.matrix >> 32)
+                                                 : 0u;
     }
+    if (a.prune_blk && a.prune_mask)
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.prune_mask_n; i += gridDim.x * blockDim.x)
+            a.prune_blk[kPruneWords + a.prune_mask + i] = 0;
     if (a.prune_blk && a.prune_len && blockIdx.x == 0)
         for (uint32_t i = threadIdx.x; i < a.prune_len_n; i += 256)
             a.prune_blk[kPruneWords + a.prune_len + i] = a.prune_lenmax[i];

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "dp_common.h"
+#include "promote_wave.h"
 
 namespace ssa {
 
@@ -210,6 +211,17 @@ __device__ __forceinline__ void prune_offer(uint32_t* pr, uint32_t lock, uint32_
     if (lane == 0) __hip_atomic_store(pr + lock, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Whether part 0 of the group (its index among the pair kernel's groups)
+// promoted this lane (kernels.h kPruneMask: a word pair per group; part 0's
+// workgroup stored it at agent scope before it released the quad's flag).
+__device__ __forceinline__ bool promoted_lane(const uint32_t* part_done, uint32_t group, int lane) {
+    const uint32_t mo = (part_done - kPruneWords)[kPruneMask];
+    if (mo == 0) return false;
+    const uint32_t w = __hip_atomic_load(part_done + mo + 2 * (size_t)group + ((uint32_t)lane >> 5), __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+    return (w >> ((uint32_t)lane & 31u)) & 1u;
+}
+
 // The kernel's argument block read again from the kernarg segment, behind an
 // opaque point: what the SW code after the strips takes from it is loaded
 // there and holds no scalar register across the DP loop (whose SGPRs are the
@@ -219,6 +231,96 @@ __device__ __forceinline__ strip_kargs* kernargs_again() {
     strip_kargs* p = (strip_kargs*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
     return p;
+}
+
+// Promotion (kernels.h kPruneMask; hand_on() below decides it): the whole
+// workgroup of a part-0 unit scores its promising lanes exactly and either
+// defers the unit's later parts with the bound of its other lanes (returns 0)
+// or, when an exact score has left the 16-bit range, sends the unit on in
+// place with nothing stored (returns 1).  That second outcome is defensive:
+// a promoted lane is a decided one, of at most nmax16 residues, and the host's
+// length bound (engine.cpp sw_rel_limit) keeps every score of such an entry
+// below kPromoteScoreMax, so no search reaches it and no test can.  It is
+// kept because the scorer's result, not the bound, is what gets stored; it
+// mirrors hand_on()'s own "go" path (sentinel, counters), and the strips that
+// follow stage their tables anew over the profile.  pmask: the calling wave's promoted
+// lanes; gl, len: the lane's index and length.  hand_on() left the waves'
+// counts at lds[2 + 2 W ..], the others' bound at lds[2 + 4 W] and a zero at
+// lds[3 + 4 W].
+// (inlined: as a called function its calling convention cost the strips'
+// column loop 3 VALU instructions per column and spills)
+template <int W>
+__device__ __forceinline__ uint32_t promote_unit(uint32_t* lds, uint64_t pmask, uint32_t gl, uint32_t len, uint32_t tid,
+                                              uint32_t wg, uint32_t pk) {
+    strip_kargs* const ka = kernargs_again();
+    uint32_t* const part_done = ka->part_done;
+    uint32_t* const pr = part_done - kPruneWords;
+    const int ln = (int)(tid & 63);
+    // The promoted lanes form one work list (a lane's place: its wave's lanes
+    // before it, behind the earlier waves'), scored round robin by the
+    // workgroup's waves, each on a SIMD of its own; the profile is shared.
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    uint32_t base = 0, total = 0;
+    for (int w = 0; w < W; w++) {
+        const uint32_t n = lds[2 + 2 * W + w];
+        base += (uint32_t)w < wv ? n : 0u;
+        total += n;
+    }
+    const bool mine = (pmask >> ln) & 1;
+    const uint32_t idx = base + (uint32_t)__popcll(pmask & ((1ull << ln) - 1));
+    if (mine) {
+        lds[kPromoteItems + 4 * idx] = gl;
+        lds[kPromoteItems + 4 * idx + 1] = len;
+        lds[kPromoteItems + 4 * idx + 2] = ka->groups[gl >> 6].blk;
+    }
+    const uint32_t qm = ka->m, alpha = ka->alpha;
+    promote_profile(lds, (const uint8_t*)((uint64_t)pr[kPruneQuery] | (uint64_t)pr[kPruneQuery + 1] << 32),
+                    (const int64_t*)((uint64_t)pr[kPruneMatrix] | (uint64_t)pr[kPruneMatrix + 1] << 32), qm, alpha, tid,
+                    64 * W);
+    __syncthreads();
+    for (uint32_t i = wv; i < total; i += W) {
+        const uint32_t igl = __builtin_amdgcn_readfirstlane(lds[kPromoteItems + 4 * i]);
+        const uint32_t ilen = __builtin_amdgcn_readfirstlane(lds[kPromoteItems + 4 * i + 1]);
+        const uint32_t iblk = __builtin_amdgcn_readfirstlane(lds[kPromoteItems + 4 * i + 2]);
+        const uint32_t s = promote_score((const uint8_t*)(ka->res + (size_t)iblk * 64 + (igl & 63u)), ilen,
+                                         (min(qm, 64u * kPromoteRL) - 1) / kPromoteRL, alpha,
+                                         ka->gap_open + ka->gap_extend, ka->gap_extend, (uint32_t)ln);
+        if (ln == 0) lds[kPromoteItems + 4 * i + 3] = s;
+    }
+    __syncthreads();
+    const uint32_t exact = mine ? lds[kPromoteItems + 4 * idx + 3] : 0u;
+    if (__ballot(exact >= kPromoteScoreMax) != 0 && ln == 0) lds[3 + 4 * W] = 1;
+    __syncthreads();
+    const bool bad = __builtin_amdgcn_readfirstlane(lds[3 + 4 * W]) != 0;
+    if (!bad && pmask != 0) {
+        // the lane's score as the kernel's end would store it, its offer to
+        // the list of final scores, and its mask bit
+        if (mine) ka->scores[ka->lane_out[gl]] = (int32_t)exact;
+        prune_offer(pr, kPruneLock2, kPruneList2, pk, exact, ln);
+        if (ln == 0) {
+            uint32_t* const mw = part_done + pr[kPruneMask] + 2 * (size_t)((gl >> 6) - ka->g_first);
+            __hip_atomic_store(mw, (uint32_t)pmask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(mw + 1, (uint32_t)(pmask >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            atomicAdd(pr + kPrunePromoted, (uint32_t)__popcll(pmask));
+        }
+    }
+    // every wave's scores and mask words complete, then the bound: the other
+    // lanes' (a deferred unit's), or the sentinel of a unit that goes in place
+    // after all
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    if (tid == 0) {
+        if (bad) {
+            atomicAdd(pr + kPruneInplace, 1u);
+            atomicAdd(pr + kPruneInplaceWaves, min((uint32_t)W, ka->ngroups - ka->g_first - wg * W));
+        }
+        __hip_atomic_store(part_done + 2 * (size_t)wg + 1, bad ? kBoundInplace : lds[2 + 4 * W], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    }
+    return bad ? 1u : 0u;
 }
 
 template <int NP, bool NW, int NPT>
@@ -386,6 +488,8 @@ pair_kernel(const StripArgs a) {
                 const uint32_t gl = g * 64 + lane;
                 const uint32_t o = a.lane_out[gl];
                 if (o == 0xffffffffu) return;
+                // (a promoted lane holds its exact score already: kernels.h kPruneMask)
+                if (promoted_lane(a.part_done, g - a.g_first, lane)) return;
                 const uint32_t len = a.lane_len[gl];
                 if (len == 0) {
                     a.scores[o] = 0;
@@ -777,7 +881,7 @@ pair_kernel(const StripArgs a) {
         // buffer stores and maxima are visible at agent scope) the part count
         uint32_t* part_done = a.part_done;
         const uint32_t* lane_out = a.lane_out;
-        uint32_t nmax16 = a.nmax16, part_epoch = a.part_epoch;
+        uint32_t nmax16 = a.nmax16, part_epoch = a.part_epoch, g_first = 0;
         if constexpr (!NW) {
             // (SW: none of these is needed before)
             strip_kargs* const ka = kernargs_again();
@@ -785,6 +889,7 @@ pair_kernel(const StripArgs a) {
             lane_out = ka->lane_out;
             nmax16 = ka->nmax16;
             part_epoch = ka->part_epoch;
+            g_first = ka->g_first;
             // (pruning and in-place work run one query: qi is 0)
             if (active) __hip_atomic_store(ka->part_smax + (size_t)qi * ka->ngroups * 64 + gl, S, __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT);
@@ -795,9 +900,22 @@ pair_kernel(const StripArgs a) {
         const uint32_t pk = NW ? 0u : __builtin_amdgcn_readfirstlane(pr[kPruneK]);
         const bool prune0 = pk != 0;
         uint32_t wbound = 0, wbest = 0;
+        // (the lane's index and length behind an opaque point, like tid: what
+        // promotion derives from them is not hoisted above the strips)
+        uint32_t glp = gl, lenp = len;
+        if constexpr (!NW) asm volatile("" : "+v"(glp), "+v"(lenp));
+        // promotion (part 0; kernels.h kPruneMask): the wave's promising lanes,
+        // how many (past the cap: one of them is too long for the scorer), and
+        // the bound of the others
+        uint64_t pmask = 0;
+        uint32_t npromo = 0, wrest = 0;
         if (prune0 && active) {
             // a lane that counts: a real entry the 16-bit patterns score exactly
-            const bool real = lane_out[gl] != 0xffffffffu && len != 0 && len <= nmax16;
+            bool real = lane_out[gl] != 0xffffffffu && len != 0 && len <= nmax16;
+            // (a lane part 0 promoted holds its final score: at a later boundary
+            // it counts neither in the unit's bound nor as promising)
+            if constexpr (!NW)
+                if (part > 0) real = real && !promoted_lane(part_done, (glp >> 6) - g_first, ln);
             const uint32_t sc = real ? sw_score(S, Rabs) : 0u;
             // Hb = max_j H(i_b, j) over the lane's own columns, from the
             // handoff boundary row this wave just wrote (low halves; column
@@ -828,7 +946,15 @@ pair_kernel(const StripArgs a) {
             wbound = wave_max_u32(lb);
             wbest = wave_max_u32(sc);
             // (once per lane: tau is the k-th of k distinct entries)
-            if (part == 0) prune_offer(pr, kPruneLock, kPruneList, pk, sc, ln);
+            if (part == 0) {
+                prune_offer(pr, kPruneLock, kPruneList, pk, sc, ln);
+                if constexpr (!NW) {
+                    const bool pl = real && sc != 0 && sc >= pr[kPruneProm];
+                    pmask = __ballot(pl);
+                    npromo = __ballot(pl && lenp > kPromoteCols) != 0 ? kPromoteCap + 1 : (uint32_t)__popcll(pmask);
+                    wrest = wave_max_u32(pl ? 0u : lb);
+                }
+            }
         }
         // every wave's device-scope stores complete, then one flag store
         __builtin_amdgcn_s_waitcnt(0);
@@ -843,6 +969,10 @@ pair_kernel(const StripArgs a) {
             if (ln == 0) {
                 lds[2 + (tid >> 6)] = wbound;
                 lds[2 + W + (tid >> 6)] = wbest;
+                if constexpr (!NW) {
+                    lds[2 + 2 * W + (tid >> 6)] = npromo;
+                    lds[2 + 3 * W + (tid >> 6)] = wrest;
+                }
             }
             __syncthreads();
             if (tid == 0) {
@@ -866,8 +996,26 @@ pair_kernel(const StripArgs a) {
                 const bool mine = part > 0 && __hip_atomic_load(part_done + 2 * (size_t)wg + 1, __ATOMIC_RELAXED,
                                                                 __HIP_MEMORY_SCOPE_AGENT) == kBoundInplace;
                 const bool go = mine || (prom != 0xffffffffu && bd >= tau && best >= prom);
-                lds[1] = mine ? 2u : go ? 1u : 0u;
-                if (!mine) {
+                // Promotion (3): a part-0 unit that would go in place scores its
+                // promising lanes exactly instead (below) and defers its later
+                // parts with the bound of its other lanes -- unless a wave holds
+                // more of them than the cap, or an undecided lane keeps the unit
+                // from ever being skipped: every later row then runs whatever
+                // tau becomes, and the unit finishes in place as before.
+                bool promote = false;
+                if constexpr (!NW)
+                    if (go && !mine && part == 0 && pr[kPruneMask] != 0) {
+                        uint32_t rest = 0, most = 0;
+                        for (int w = 0; w < W; w++) {
+                            most = max(most, lds[2 + 2 * W + w]);
+                            rest = max(rest, lds[2 + 3 * W + w]);
+                        }
+                        promote = most >= 1 && most <= kPromoteCap && rest != kBoundNever;
+                        lds[2 + 4 * W] = rest;
+                        lds[3 + 4 * W] = 0;      // (a promoted lane's exact score left the 16-bit range)
+                    }
+                lds[1] = mine ? 2u : promote ? 3u : go ? 1u : 0u;
+                if (!mine && !promote) {
                     if (go) {
                         // (and its waves that hold a group: each reports its end, kPruneInplaceDone)
                         strip_kargs* const ka = kernargs_again();
@@ -882,6 +1030,8 @@ pair_kernel(const StripArgs a) {
             }
             __syncthreads();
             inplace = __builtin_amdgcn_readfirstlane(lds[1]);
+            if constexpr (!NW)
+                if (inplace == 3) inplace = promote_unit<W>(lds, pmask, glp, lenp, tid, wg, pk);
         }
         if (tid == 0 && inplace != 2)
             __hip_atomic_store(part_done + 2 * ((size_t)wg * nqs + qi), part_epoch + part, __ATOMIC_RELAXED,
@@ -930,7 +1080,9 @@ pair_kernel(const StripArgs a) {
         uint32_t* const pr = ka->part_done - kPruneWords;
         const uint32_t pk = __builtin_amdgcn_readfirstlane(pr[kPruneK]);
         if (pk != 0) {
-            const bool real = o != 0xffffffffu && len != 0 && len <= ka->nmax16;
+            // (a lane part 0 promoted has offered this score already: once per list)
+            const bool real = o != 0xffffffffu && len != 0 && len <= ka->nmax16 &&
+                              !(split && part > 0 && promoted_lane(ka->part_done, (gl >> 6) - ka->g_first, lane));
             prune_offer(pr, kPruneLock2, kPruneList2, pk, real ? sw_score(S, Rabs) : 0u, lane);
             // a wave of a unit that finished in place (it still finds its own
             // sentinel: a deferred unit that found one has returned) reports
