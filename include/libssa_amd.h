@@ -368,6 +368,68 @@ size_t ssa_amd_search_above( p_query query, int algo, int64_t min_score, int bit
 size_t ssa_amd_merge_above( const ssa_hit_t * hits, size_t n, int64_t min_score,
                             ssa_hit_t * out, size_t cap, size_t * total );
 
+/* Profile search: a position-specific scoring matrix (PSSM) in the query's
+ * place.  A profile has one row of 32 residue scores per query
+ * position, where a sequence query has one residue.
+ *
+ * Recurrence and conventions: exactly sw_align's / nw_align's (the reference's
+ * full_sw / full_nw, affine gaps, the current init_gap_penalties), with the
+ * substitution score M[d_j][q_i] replaced by scores[i * 32 + d_j].  The
+ * empty-DB-entry conventions are unchanged (SW 0; such records are no entries
+ * of a search).  The matrix set by init_score_matrix / init_constant_scores is
+ * NOT read and need not be initialised.  There is no bit width: scores are
+ * exact, as at every width of the sequence calls, and the reference's 8/16-bit
+ * overflow counters are not computed (stats counters, overflow_8 and
+ * overflow_16 read 0).
+ *
+ * Not done for a profile view (each may be lifted later): top-k pruning and
+ * promotion, the rare-code merge, fused batches and the overflow-counter
+ * kernels -- stats pruned_units, inplace_units, pruned_first, rare_merged,
+ * ssa_amd_get_pruned_whole() and ssa_amd_get_promoted_lanes() read 0.
+ * Alignments (CIGARs, ssa_amd_align_hits, ssa_amd_summarize_hits) are not
+ * offered for profile hits. */
+typedef struct ssa_amd_profile * p_ssa_profile;
+
+/* rows >= 1 position rows of 32 scores: scores[i * 32 + c] is the score of DB residue code c
+ * (a DB-side mapped code of the symbol type in force, what ssa_amd_map_residues writes; 0..31)
+ * at query position i.  Every value must lie in [-32768, 32767].  The scores are copied.
+ * NULL for scores == NULL, rows == 0, or a value out of range. */
+p_ssa_profile ssa_amd_profile_create( const int32_t * scores, size_t rows );
+/* The profile a sequence query IS under the current matrix: row i = M[c][q_i] for view `view`
+ * of `query` (ssa_amd_query_views' order).  NULL for a NULL query, a bad view, an empty view,
+ * or a matrix value outside [-32768, 32767]. */
+p_ssa_profile ssa_amd_profile_from_query( p_query query, size_t view );
+size_t ssa_amd_profile_rows( p_ssa_profile p );     /* 0 for NULL */
+void   ssa_amd_profile_free( p_ssa_profile p );     /* NULL is allowed */
+
+/* Host only, no device, no DB: the definition.  scores[e] of profile p against the n sequences
+ * d_codes[d_off[e] .. d_off[e+1]), int64, algo SSA_AMD_SW / SSA_AMD_NW, current gap penalties,
+ * on set_thread_count threads.  An empty sequence scores 0 (SW) or the boundary value
+ * gap_open + rows * gap_extend (NW).
+ * Non-zero (nothing written) for NULL arguments with n > 0, decreasing offsets, a code >= 32
+ * or an unknown algo. */
+int ssa_amd_profile_score_host( p_ssa_profile p, int algo, const uint8_t * d_codes,
+                                const uint64_t * d_off, size_t n, int64_t * scores );
+
+/* ssa_amd_search / ssa_amd_search_above with a profile in the query's place.  A profile is one
+ * query view: every hit's query_id is 0; db_id, db_strand and db_frame are filled as
+ * ssa_amd_search fills them, for every entry the open DB has (AMINOACID, NUCLEOTIDE with one or
+ * both strands, TRANS_DB).  A symbol type that translates the query (TRANS_QUERY, TRANS_BOTH)
+ * has no meaning for a profile: the call prints a warning and returns 0 with nothing launched,
+ * and so does a NULL profile.  Orders and modes are the sequence calls': SSA_AMD_TOPK's order and
+ * tie IDs are the reference heap replay, SSA_AMD_LOG is the insertion log (ssa_amd_replay,
+ * ssa_amd_merge_logs and ssa_amd_gather_logs work on it unchanged), the threshold order is
+ * ssa_amd_search_above's (ssa_amd_merge_above works on its lists), and several device slots
+ * give the single-device result.  ssa_amd_get_stats reports the call as a search. */
+size_t ssa_amd_search_profile( p_ssa_profile p, int algo, size_t hitcount, int mode,
+                               ssa_hit_t * out, size_t cap );
+size_t ssa_amd_search_profile_above( p_ssa_profile p, int algo, int64_t min_score,
+                                     ssa_hit_t * out, size_t cap, size_t * total );
+/* Bytes the last search staged for its per-search upload on the first device slot (the scoring
+ * block -- the 8 KB matrix, or a profile's position scores -- the query codes, and the strip
+ * kernels' table when those run); beside ssa_amd_stats_t, whose layout is kept. */
+uint64_t ssa_amd_get_upload_bytes( void );
+
 /* Replays an insertion log (concatenated shard logs, in shard order) and
  * writes the sorted top-k (score desc, id desc).  Returns the count. */
 size_t ssa_amd_replay( const ssa_hit_t * log, size_t n, size_t hitcount, ssa_hit_t * out );

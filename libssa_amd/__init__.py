@@ -135,7 +135,10 @@ EXPORTS = {
                       "ssa_amd_get_align_hits_stats", "ssa_amd_summarize_pairs_local",
                       "ssa_amd_score_pairs_xdrop", "ssa_amd_align_pairs_xdrop", "ssa_amd_summarize_pairs_xdrop",
                       "ssa_amd_get_xdrop_dropped", "ssa_amd_search_above", "ssa_amd_merge_above",
-                      "ssa_amd_summarize_hits", "ssa_amd_get_summarize_hits_stats"],
+                      "ssa_amd_summarize_hits", "ssa_amd_get_summarize_hits_stats",
+                      "ssa_amd_profile_create", "ssa_amd_profile_from_query", "ssa_amd_profile_rows",
+                      "ssa_amd_profile_free", "ssa_amd_profile_score_host", "ssa_amd_search_profile",
+                      "ssa_amd_search_profile_above", "ssa_amd_get_upload_bytes"],
     "libssa_fasta_db.so": ["ssa_db_init", "ssa_db_get_sequence_count", "ssa_db_get_sequence", "ssa_db_close"],
 }
 
@@ -225,6 +228,14 @@ def load():
         "ssa_amd_summarize_hits": ([P, c_int, c_void_p, c_size_t, c_void_p], c_int),
         "ssa_amd_get_summarize_hits_stats": ([POINTER(ssa_amd_hits_stats_t)], None),
         "ssa_amd_map_residues": ([c_char_p, c_size_t, c_char_p, c_size_t], c_size_t),
+        "ssa_amd_profile_create": ([c_void_p, c_size_t], P),
+        "ssa_amd_profile_from_query": ([P, c_size_t], P),
+        "ssa_amd_profile_rows": ([P], c_size_t), "ssa_amd_profile_free": ([P], None),
+        "ssa_amd_profile_score_host": ([P, c_int, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+        "ssa_amd_search_profile": ([P, c_int, c_size_t, c_int, POINTER(ssa_hit_t), c_size_t], c_size_t),
+        "ssa_amd_search_profile_above": ([P, c_int, c_int64, POINTER(ssa_hit_t), c_size_t, POINTER(c_size_t)],
+                                         c_size_t),
+        "ssa_amd_get_upload_bytes": ([], c_uint64),
         "ssa_amd_shard_bounds": ([c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_size_t)], c_int),
     }
     for name, (args, res) in sig.items():
@@ -444,6 +455,84 @@ def search_above(q, algo, min_score, bit_width=BIT_WIDTH_16, cap=None):
     buf = _hits(cap)
     n = L.ssa_amd_search_above(q, algo, min_score, bit_width, buf, cap, ctypes.byref(total))
     return _hit_tuples(buf, n), total.value
+
+
+def profile_create(rows):
+    """ssa_amd_profile_create: a profile from an int array [rows, 32], rows[i][c]
+    the score of DB residue code c at query position i, every value within
+    [-32768, 32767].  Returns the handle, or None when the library refuses it
+    (no rows, a value out of range).  Free it with profile_free."""
+    import numpy as np
+    a = np.asarray(rows)
+    if a.ndim != 2 or a.shape[1] != 32 or a.dtype.kind not in "iu":
+        raise ValueError("profile_create: an integer array [rows, 32] expected")
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        return None                 # (no int32: out of the profile's range anyway)
+    a = np.ascontiguousarray(a, np.int32)
+    return load().ssa_amd_profile_create(a.ctypes.data if a.size else None, a.shape[0])
+
+
+def profile_from_query(q, view=0):
+    """ssa_amd_profile_from_query: the profile that view `view` of the sequence
+    query q is under the current matrix (None for a bad or empty view)."""
+    return load().ssa_amd_profile_from_query(q, view)
+
+
+def profile_rows(p): return load().ssa_amd_profile_rows(p)
+def profile_free(p): load().ssa_amd_profile_free(p)
+
+
+def profile_score_host(p, algo, codes, off):
+    """ssa_amd_profile_score_host: the exact int64 scores of profile p against
+    the sequences codes[off[e]:off[e + 1]] (uint8 codes, uint64 offsets), on the
+    host.  Raises ValueError when the library refuses the arguments."""
+    import numpy as np
+    codes = np.ascontiguousarray(codes, np.uint8)
+    off = np.ascontiguousarray(off, np.uint64)
+    if len(off) < 1:
+        raise ValueError("profile_score_host: an offset array of n + 1 entries expected")
+    n = len(off) - 1
+    out = np.zeros(n, np.int64)
+    rc = load().ssa_amd_profile_score_host(p, algo, codes.ctypes.data, off.ctypes.data, n, out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ssa_amd_profile_score_host refused its arguments ({rc})")
+    return out
+
+
+def search_profile(p, algo, hitcount, mode=TOPK, cap=None):
+    """ssa_amd_search_profile: search()'s result with profile p in the query's place."""
+    L = load()
+    explicit = cap is not None
+    if cap is None:
+        cap = max(hitcount, 1) if mode == TOPK else max(4 * hitcount + 4096, 65536)
+    while True:
+        buf = _hits(cap)
+        n = L.ssa_amd_search_profile(p, algo, hitcount, mode, buf, cap)
+        if n < cap or explicit or mode == TOPK:
+            break
+        cap *= 4            # a log filled the buffer: search again with room
+    return _hit_tuples(buf, n)
+
+
+def search_profile_above(p, algo, min_score, cap=None):
+    """ssa_amd_search_profile_above: search_above()'s (hits, total) with profile p
+    in the query's place."""
+    _above_args(min_score, cap)
+    L = load()
+    total = c_size_t(0)
+    if cap is None or cap == 0:
+        L.ssa_amd_search_profile_above(p, algo, min_score, None, 0, ctypes.byref(total))
+        if cap == 0 or total.value == 0:
+            return [], total.value
+        cap = total.value
+    buf = _hits(cap)
+    n = L.ssa_amd_search_profile_above(p, algo, min_score, buf, cap, ctypes.byref(total))
+    return _hit_tuples(buf, n), total.value
+
+
+def upload_bytes():
+    """ssa_amd_get_upload_bytes: bytes the last search staged for its per-search upload."""
+    return int(load().ssa_amd_get_upload_bytes())
 
 
 def merge_above(hits, min_score, cap=None):

@@ -37,6 +37,12 @@ uint32_t& promoted_lanes_stat() {
     return n;
 }
 
+// ... and the bytes its per-search upload staged for the first device slot (ssa_amd_get_upload_bytes)
+uint64_t& upload_bytes_stat() {
+    static uint64_t n = 0;
+    return n;
+}
+
 // The environment's device list as the search uses it: its first
 // set_thread_count() devices -- the reference's thread count is its number of
 // search workers (thread_pool.c:39-47), a device slot's analogue here; 0 (the
@@ -247,6 +253,7 @@ void publish_stats(const std::vector<SearchScores>& sc, const std::vector<SlotPl
     ssa_amd_stats_t& S = stats();
     S.kernel_ms = S.wide_ms = S.d2h_ms = S.prep_ms = S.upload_ms = S.sync_wait_ms = 0;
     S.cells = S.entries = S.wide_count = S.kernel_bytes = S.filter_candidates = 0;
+    upload_bytes_stat() = sc.empty() ? 0 : sc[0].upload_bytes;
     S.slots = (uint32_t)std::min(sc.size(), (size_t)16);
     for (size_t i = 0; i < 16; i++) {
         S.slot_device[i] = i < S.slots ? plan[i].device : -1;
@@ -294,12 +301,13 @@ void publish_stats(const std::vector<SearchScores>& sc, const std::vector<SlotPl
 void finish_search(const std::vector<SearchScores>& sc, const std::vector<SlotPlan>& plan,
                    const std::vector<double>& slot_ms, int bw, double t0, double t1, double t2);
 
-void run_search(p_query q, int algo, size_t k, int bw, bool want_log, SearchResult& R) {
+// R.views: the search's query views, set by the caller (a p_query's, or a
+// profile's single view -- then bw is BIT_WIDTH_64 and nothing is pruned)
+void run_search_views(int algo, size_t k, int bw, bool want_log, SearchResult& R) {
     const double t0 = now_ms();
     check_width(bw);
     ensure_device_db();
     const std::vector<SlotPlan> plan = device_plan();
-    R.views = query_views(q);
     host_mark("views");
     std::vector<SearchScores> sc(plan.size());
     std::vector<std::vector<Hit>> logs(plan.size());
@@ -344,6 +352,11 @@ void run_search(p_query q, int algo, size_t k, int bw, bool want_log, SearchResu
     }
     if (!want_log) R.hits = heap.sorted();
     finish_search(sc, plan, slot_ms, bw, t0, t1, now_ms());
+}
+
+void run_search(p_query q, int algo, size_t k, int bw, bool want_log, SearchResult& R) {
+    R.views = query_views(q);
+    run_search_views(algo, k, bw, want_log, R);
 }
 
 // What every search call ends with: the statistics (t0 the call's start, t1
@@ -445,12 +458,12 @@ void collect_above(const SearchScores& sc, const EntryMeta& meta, int64_t min_sc
 // ssa_amd_search_above: run_search's counterpart.  Every slot searches its
 // shard with the threshold (device_search's `above`) and collects its hits,
 // on its pool thread; the slots' lists go through merge_above together.
-std::vector<Hit> run_search_above(p_query q, int algo, int64_t min_score, int bw, size_t cap, size_t* total) {
+std::vector<Hit> run_search_above(const std::vector<QueryView>& views, int algo, int64_t min_score, int bw, size_t cap,
+                                  size_t* total) {
     const double t0 = now_ms();
     check_width(bw);
     ensure_device_db();
     const std::vector<SlotPlan> plan = device_plan();
-    const std::vector<QueryView> views = query_views(q);
     std::vector<SearchScores> sc(plan.size());
     std::vector<std::vector<Hit>> lists(plan.size());
     std::vector<double> slot_ms(plan.size(), 0.0);
@@ -1123,12 +1136,65 @@ size_t ssa_amd_search_above(p_query query, int algo, int64_t min_score, int bit_
                             size_t* total) {
     test_configuration(query);
     if (!out) cap = 0;
-    const std::vector<Hit> v = run_search_above(query, algo == SSA_AMD_NW ? kAlgoNW : kAlgoSW, min_score, bit_width,
-                                                cap, total);
+    const std::vector<Hit> v = run_search_above(query_views(query), algo == SSA_AMD_NW ? kAlgoNW : kAlgoSW, min_score,
+                                                bit_width, cap, total);
     for (size_t i = 0; i < v.size(); i++)
         out[i] = ssa_hit_t{v[i].score, v[i].id, v[i].qid, v[i].strand, v[i].frame, {0, 0, 0, 0, 0}};
     return v.size();
 }
+
+// A profile in the query's place: its single view, or nothing (with a warning)
+// for a NULL profile or a symbol type that translates the query.  The matrix
+// is not read, so test_configuration's matrix checks do not apply.
+static bool profile_view(p_ssa_profile p, std::vector<QueryView>& views) {
+    if (!p) {
+        print_warning("Profile not initialized. Nothing searched.");
+        return false;
+    }
+    if (cfg().symtype == TRANS_QUERY || cfg().symtype == TRANS_BOTH) {
+        print_warning("A profile cannot be translated: symbol type %d translates the query. Nothing searched.", cfg().symtype);
+        return false;
+    }
+    if (!cfg().gap_open && !cfg().gap_extend)
+        print_warning("Gap opening and gap extension cost set to zero. Possible error.");
+    if (ssa_db_get_sequence_count() == 0) print_warning("Database contains zero sequences. Possible error.");
+    QueryView v{};
+    v.seq = nullptr;
+    v.len = p->nrows;
+    v.prof = p->rows.data();
+    views.assign(1, v);
+    return true;
+}
+
+size_t ssa_amd_search_profile(p_ssa_profile p, int algo, size_t hitcount, int mode, ssa_hit_t* out, size_t cap) {
+    SearchResult R;
+    if (!profile_view(p, R.views)) return 0;
+    // (BIT_WIDTH_64: no overflow counters; device_search never prunes a profile view)
+    run_search_views(algo == SSA_AMD_NW ? kAlgoNW : kAlgoSW, hitcount, BIT_WIDTH_64, mode == SSA_AMD_LOG, R);
+    stats().counters = 0;
+    const size_t n = out ? std::min(cap, R.hits.size()) : 0;
+    for (size_t i = 0; i < n; i++) {
+        const Hit& h = R.hits[i];
+        out[i] = ssa_hit_t{h.score, h.id, h.qid, h.strand, h.frame, {0, 0, 0, 0, 0}};
+    }
+    return n;
+}
+
+size_t ssa_amd_search_profile_above(p_ssa_profile p, int algo, int64_t min_score, ssa_hit_t* out, size_t cap,
+                                    size_t* total) {
+    std::vector<QueryView> views;
+    if (total) *total = 0;
+    if (!profile_view(p, views)) return 0;
+    if (!out) cap = 0;
+    const std::vector<Hit> v = run_search_above(views, algo == SSA_AMD_NW ? kAlgoNW : kAlgoSW, min_score, BIT_WIDTH_64,
+                                                cap, total);
+    stats().counters = 0;
+    for (size_t i = 0; i < v.size(); i++)
+        out[i] = ssa_hit_t{v[i].score, v[i].id, v[i].qid, v[i].strand, v[i].frame, {0, 0, 0, 0, 0}};
+    return v.size();
+}
+
+uint64_t ssa_amd_get_upload_bytes(void) { return upload_bytes_stat(); }
 
 size_t ssa_amd_merge_above(const ssa_hit_t* hits, size_t n, int64_t min_score, ssa_hit_t* out, size_t cap,
                            size_t* total) {

@@ -179,8 +179,23 @@ struct QueryView {                // one search "query buffer" (searcher.c:42-90
     size_t len;
     int strand, frame;
     char* cseq;                   // pointer handed out in q_seq_t.seq
+    // a profile view (ssa_amd_search_profile): seq == nullptr and `len` position
+    // rows of 32 scores, prof[i * 32 + c] = DB residue code c at query row i
+    const int32_t* prof = nullptr;
 };
 std::vector<QueryView> query_views(p_query q);
+}  // namespace ssa
+
+// a position-specific scoring matrix (ssa_amd_profile_create)
+struct ssa_amd_profile {
+    std::vector<int32_t> rows;    // [nrows][32]
+    size_t nrows = 0;
+};
+
+namespace ssa {
+// profile.cpp: ssa_amd_profile_score_host, the profile recurrences' definition
+int profile_score_host(const ssa_amd_profile* p, int algo, const uint8_t* d_codes, const uint64_t* d_off, size_t n,
+                       int64_t* scores);
 
 // ---------------------------------------------------------------- top-k
 struct Hit {

@@ -1075,8 +1075,14 @@ struct ViewPlan {
     std::vector<uint8_t> cls_of, cls_rep;
     bool use_cls = false;
     // the kernels' codes' profile rows: crow[c * 32 + y] = score of kernel
-    // code c against query code y (a class's representative row)
+    // code c against query code y (a class's representative row); a profile
+    // view's: crow[c * cpitch + i] = score of kernel code c at query row i
+    // (cpitch the row count rounded up to 4, the device's LongArgs::pitch).
+    // Read through at()
     std::vector<int64_t> crow;
+    size_t cpitch = 32;
+    // P(c, i): the score of kernel code c at row i of the view the plan was made for
+    int64_t at(const QueryView& qv, uint32_t c, size_t i) const { return crow[(size_t)c * cpitch + (qv.seq ? qv.seq[i] : i)]; }
     uint32_t A = 0, prow = 0;
     int64_t minM = 0, maxM = 0;
     uint32_t nmax16 = 0, nw_base = 0, long_groups = 0;
@@ -1112,6 +1118,13 @@ static void plan_view(const DeviceDB& D, const QueryView& qv, bool nw, int np, c
     const int64_t* M = matrix().m;
     const size_t m = qv.len;
     const size_t ml = force ? force->m : m;        // row count of the length limits
+    const bool profile = qv.seq == nullptr && qv.prof != nullptr;
+    // the score of DB residue code x (not yet compact) at row i: the matrix
+    // entry of the row's residue, or the profile's own value (the matrix is
+    // not read for a profile view)
+    auto raw = [&](uint32_t x, size_t i) -> int64_t {
+        return profile ? (int64_t)qv.prof[i * 32 + x] : M[((size_t)x << 5) + qv.seq[i]];
+    };
     vp = ViewPlan();
     std::vector<uint8_t>& cls_of = vp.cls_of;
     std::vector<uint8_t>& cls_rep = vp.cls_rep;
@@ -1122,7 +1135,20 @@ static void plan_view(const DeviceDB& D, const QueryView& qv, bool nw, int np, c
     // 28-symbol DB: '-', U, O and X score alike against a standard-residue
     // query -> 25 classes, a 75.7 KiB table, two workgroups per CU instead
     // of none); the class-coded residues are cached per class map.
-    {
+    if (profile) {
+        // a profile: DB codes whose columns agree on every row
+        cls_of.resize(D.alpha);
+        for (uint32_t c = 0; c < D.alpha; c++) {
+            size_t k = 0;
+            for (; k < cls_rep.size(); k++) {
+                bool same = true;
+                for (size_t i = 0; i < m && same; i++) same = qv.prof[i * 32 + D.code_of[c]] == qv.prof[i * 32 + cls_rep[k]];
+                if (same) break;
+            }
+            if (k == cls_rep.size()) cls_rep.push_back(D.code_of[c]);
+            cls_of[c] = (uint8_t)k;
+        }
+    } else {
         uint32_t qset = 0;
         for (size_t i = 0; i < m; i++) qset |= 1u << (qv.seq[i] & 31);
         cls_of.resize(D.alpha);
@@ -1161,7 +1187,7 @@ static void plan_view(const DeviceDB& D, const QueryView& qv, bool nw, int np, c
     // so the result is unchanged.  Only while those entries stay a small
     // share (a quarter of the DB at most) and the tier is exact for them.
     int ub = -1;
-    if (allow_merge && C.rare_merge && C.sw_kernel == 0 && np == 16 && !D.code_entries.empty() && m > 0) {
+    if (allow_merge && !profile && C.rare_merge && C.sw_kernel == 0 && np == 16 && !D.code_entries.empty() && m > 0) {
         const size_t A0 = cls_rep.size();
         int64_t xlo = INT64_MAX, xhi = INT64_MIN;        // the exact re-score's profile bounds
         for (size_t i = 0; i < m; i++)
@@ -1215,8 +1241,15 @@ static void plan_view(const DeviceDB& D, const QueryView& qv, bool nw, int np, c
     // kernel codes: the classes, or the compact codes themselves
     uint32_t A = use_cls ? (uint32_t)cls_rep.size() : D.alpha;
     std::vector<int64_t>& crow = vp.crow;
-    crow.assign((size_t)std::max<uint32_t>(A, 1) * 32, -1);
-    for (uint32_t c = 0; c < A; c++)
+    if (profile) {
+        vp.cpitch = std::max<size_t>((m + 3) & ~(size_t)3, 4);
+        crow.assign((size_t)std::max<uint32_t>(A, 1) * vp.cpitch, -1);
+        for (uint32_t c = 0; c < A; c++)
+            for (size_t i = 0; i < m; i++) crow[(size_t)c * vp.cpitch + i] = raw(use_cls ? cls_rep[c] : D.code_of[c], i);
+    } else {
+        crow.assign((size_t)std::max<uint32_t>(A, 1) * 32, -1);
+    }
+    for (uint32_t c = 0; c < A && !profile; c++)
         if ((int)c != ub) memcpy(&crow[(size_t)c * 32], M + ((size_t)(use_cls ? cls_rep[c] : D.code_of[c]) << 5), 32 * 8);
     if (ub >= 0) {
         // the upper-bound class: the maximum of its members' rows
@@ -1232,7 +1265,7 @@ static void plan_view(const DeviceDB& D, const QueryView& qv, bool nw, int np, c
     int64_t minM = INT64_MAX, maxM = INT64_MIN;
     for (size_t i = 0; i < m; i++)
         for (uint32_t c = 0; c < A; c++) {
-            const int64_t x = crow[(size_t)c * 32 + qv.seq[i]];
+            const int64_t x = vp.at(qv, c, i);
             minM = std::min(minM, x);
             maxM = std::max(maxM, x);
         }
@@ -1348,6 +1381,10 @@ static void plan_view(const DeviceDB& D, const QueryView& qv, bool nw, int np, c
 struct PlanCache {
     struct Entry {
         std::vector<uint8_t> seq;
+        // a profile view's rows (the key is its contents: two profiles of one
+        // length, or a profile and a sequence, never share a plan)
+        std::vector<int32_t> prof;
+        bool profile = false;
         uint64_t gen = 0, used = 0;
         int np = 0;
         bool nw = false, merge = false, batch = false;
@@ -1362,9 +1399,14 @@ static void cached_plan(DeviceDB& D, const QueryView& qv, bool nw, int np, ViewP
     if (!D.plans) D.plans = std::make_shared<PlanCache>();
     PlanCache& P = *D.plans;
     const uint64_t gen = cfg().plan_gen;
+    const bool profile = qv.seq == nullptr;
+    auto same_query = [&](const PlanCache::Entry& x) {
+        if (x.profile != profile) return false;
+        if (profile) return x.prof.size() == qv.len * 32 && !memcmp(x.prof.data(), qv.prof, qv.len * 32 * sizeof(int32_t));
+        return x.seq.size() == qv.len && (qv.len == 0 || !memcmp(x.seq.data(), qv.seq, qv.len));
+    };
     for (auto& x : P.e)
-        if (x.gen == gen && x.np == np && x.nw == nw && x.merge == allow_merge && !x.batch && x.seq.size() == qv.len &&
-            (qv.len == 0 || !memcmp(x.seq.data(), qv.seq, qv.len))) {
+        if (x.gen == gen && x.np == np && x.nw == nw && x.merge == allow_merge && !x.batch && same_query(x)) {
             x.used = ++P.clock;
             vp = x.vp;
             return;
@@ -1379,7 +1421,14 @@ static void cached_plan(DeviceDB& D, const QueryView& qv, bool nw, int np, ViewP
         for (auto& x : P.e)
             if (x.used < slot->used) slot = &x;
     }
-    slot->seq.assign(qv.seq, qv.seq + qv.len);
+    slot->profile = profile;
+    if (profile) {
+        slot->seq.clear();
+        slot->prof.assign(qv.prof, qv.prof + qv.len * 32);
+    } else {
+        slot->prof.clear();
+        slot->seq.assign(qv.seq, qv.seq + qv.len);
+    }
     slot->gen = gen;
     slot->np = np;
     slot->nw = nw;
@@ -1499,7 +1548,11 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     // flags, summed on the device after the last view -- only when someone
     // observes them (m_run prints them at OUTPUT_INFO, manager.c:157-160;
     // option "counters")
-    const bool want_counts = bw != BIT_WIDTH_64 && E > 0 && V > 0 && counters_on(cfg());
+    // a profile view (ssa_amd_search_profile): one view, never in a batch; no
+    // overflow counters, rare-code merge or pruning (engine.h)
+    const bool profile = V > 0 && views[0].seq == nullptr && views[0].prof != nullptr;
+    if (profile && (V != 1 || indep)) fatal("device_search: a profile is one query view");
+    const bool want_counts = bw != BIT_WIDTH_64 && E > 0 && V > 0 && counters_on(cfg()) && !profile;
     bool counted = false;
     if (want_counts && D.flags_cap < V * E) {
         dfree(D.d_flags);
@@ -1562,7 +1615,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
     const bool lean = C.lean_events != 0;   // (option "lean_events": no upload/tier/filter markers)
     // the rare-code merge (plan_view) needs the single-pass filter and no
     // counters (they decide from exact scores)
-    const bool allow_merge = C.rare_merge && V == 1 && !ind && out.sparse && !want_counts && E > 0 && !above;
+    const bool allow_merge = C.rare_merge && V == 1 && !ind && out.sparse && !want_counts && E > 0 && !above && !profile;
     if (allow_merge && D.alpha > 21) ensure_entry_masks(D);
     // every lane fits a view's overflow list (reference: no limit on the
     // sequences search_16.c:101-109 re-runs at 64 bits)
@@ -1813,10 +1866,9 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
         // (the pair kernel's tables are built on the device: pair_tables_kernel)
         std::vector<uint16_t> P(use_pair ? 0 : (size_t)(A + 1) * mpad, (uint16_t)padv);
         for (uint32_t c = 0; c < (use_pair ? 0u : A); c++) {
-            const int64_t* row = vp.crow.data() + (size_t)c * 32;
             uint16_t* pc = P.data() + (size_t)c * mpad;
             for (size_t i = 0; i < m; i++)
-                pc[i] = (uint16_t)(int16_t)std::max<int64_t>(-32768, std::min<int64_t>(32767, row[qv.seq[i]] + rel));
+                pc[i] = (uint16_t)(int16_t)std::max<int64_t>(-32768, std::min<int64_t>(32767, vp.at(qv, c, i) + rel));
         }
         auto prow_of = [&](uint32_t c) { return P.data() + (size_t)std::min(c, A) * mpad; };
         auto val = [&](uint32_t c, size_t i) -> int16_t { return (int16_t)prow_of(c)[i]; };
@@ -1837,9 +1889,15 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     }
         }
         // the kernel codes' matrix (every kernel reads residues in kernel codes)
+        // (a profile view uploads its position scores, vp.crow itself, in the
+        // matrix's place -- [A][cpitch] int64, as the kernels load them
+        // (kernels.h prof_val) -- and no query codes)
         int64_t Mc[1024];
-        for (int x = 0; x < 32; x++)
+        for (int x = 0; x < 32 && !profile; x++)
             for (int y = 0; y < 32; y++) Mc[(x << 5) + y] = (uint32_t)x < A ? vp.crow[(size_t)x * 32 + y] : -1;
+        const uint32_t pitch = profile ? (uint32_t)vp.cpitch : 0u;
+        const size_t up_hdr = profile ? (vp.crow.size() * 8 + 15) & ~(size_t)15 : kUpHeader;
+        const size_t mq = profile ? 0 : m;   // bytes of query codes in the block
         const uint32_t wide_threads = (uint32_t)(std::max<size_t>(64, std::min<size_t>(16384, (64ull << 20) / (16 * m))) / 64 * 64);
         // a multi-view search's earlier views may still be queued on the
         // stream: drain it before a device buffer they read is reallocated
@@ -1896,7 +1954,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
         // device upload block: [matrix 8 KB][top boundary][query codes]
         // (+ a fused batch's row counts, view 0: StripArgs::qm)
         const size_t top_bytes = (top.size() * 4 + 15) & ~(size_t)15;
-        const size_t qm_off = (kUpHeader + top_bytes + m + 3) & ~(size_t)3;
+        const size_t qm_off = (up_hdr + top_bytes + mq + 3) & ~(size_t)3;
         // (+ a search that may be pruned: lenmax[0 .. m], the most an entry of
         // L residues can score -- the sum of the min(L, m) largest row maxima
         // of the profile, on the codes the kernel scores with.  A local
@@ -1909,7 +1967,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             std::vector<int64_t> rowmax(m);
             for (size_t i = 0; i < m; i++) {
                 int64_t best = 0;
-                for (uint32_t c = 0; c < A; c++) best = std::max(best, vp.crow[(size_t)c * 32 + qv.seq[i]]);
+                for (uint32_t c = 0; c < A; c++) best = std::max(best, vp.at(qv, c, i));
                 rowmax[i] = best;
             }
             std::sort(rowmax.begin(), rowmax.end(), std::greater<int64_t>());
@@ -1923,7 +1981,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
         }
         const size_t blk_bytes = (fused && v == 0) ? qm_off + 4 * V
                                  : len_want        ? qm_off + 4 * lenmax.size()
-                                                   : kUpHeader + top_bytes + m;
+                                                   : up_hdr + top_bytes + mq;
         const size_t up_bytes = blk_bytes + 16 + qpt.size() * 4;
         // the staging buffer is reused: in a multi-view search the previous
         // view's copies may still be queued behind its predecessor's kernel
@@ -1960,15 +2018,19 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             dqpt = D.d_qpt;
         }
         D.d_matrix = (int64_t*)dup;
-        D.d_top = top_cached ? D.d_topc : (uint32_t*)(dup + kUpHeader);
-        D.d_query = dup + kUpHeader + top_bytes;
+        D.d_top = top_cached ? D.d_topc : (uint32_t*)(dup + up_hdr);
+        D.d_query = dup + up_hdr + top_bytes;
         // staging mirrors the device block, then the strip kernels' table
         uint8_t* up_m = hup;
-        uint8_t* up_t = up_m + kUpHeader;
+        uint8_t* up_t = up_m + up_hdr;
         uint8_t* up_s = up_t + top_bytes;
         uint8_t* up_q = hup + ((blk_bytes + 15) & ~(size_t)15);
-        memcpy(up_m, Mc, 1024 * 8);
-        for (int y = 0; y < 32; y++) memcpy(up_m + 8192 + 8 * y, &M[y], 8);   // code 0's row, M[0][y]
+        if (profile) {
+            memcpy(up_m, vp.crow.data(), vp.crow.size() * 8);
+        } else {
+            memcpy(up_m, Mc, 1024 * 8);
+            for (int y = 0; y < 32; y++) memcpy(up_m + 8192 + 8 * y, &M[y], 8);   // code 0's row, M[0][y]
+        }
         if (merge) {
             // the compact codes' matrix: the exact re-score of merged-code entries
             int64_t* mx = (int64_t*)(up_m + kUpExactMat);
@@ -1977,7 +2039,8 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                     mx[(x << 5) + y] = (uint32_t)x < D.alpha ? M[((size_t)D.code_of[x] << 5) + y] : -1;
         }
         if (!top.empty()) memcpy(up_t, top.data(), top.size() * 4);
-        memcpy(up_s, qv.seq, m);
+        if (!profile) memcpy(up_s, qv.seq, m);
+        if (v == 0) out.upload_bytes = blk_bytes + qpt.size() * 4;
         if (fused && v == 0)
             for (size_t i = 0; i < V; i++) {
                 const uint32_t mi = (uint32_t)views[i].len;
@@ -2033,6 +2096,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
         w.gap_extend = R;
         w.nw = nw ? 1 : 0;
         w.ovf_cap = (uint32_t)ovf_capv;
+        w.pitch = pitch;
         // the counters of the filter pass that follows this wide kernel
         if (ind) w.zero = (uint32_t*)((uint8_t*)D.d_fbuf + v * dreg);
         else if (out.sparse && v + 1 == V) w.zero = D.d_fbuf;
@@ -2061,6 +2125,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             ra.lane_out = D.d_lane_out;
             ra.query = D.d_query;
             ra.matrix = D.d_matrix;
+            ra.pitch = pitch;
             ra.m = (uint32_t)m;
             ra.alpha = A;
             ra.gap_open = Q;
@@ -2151,6 +2216,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             la.query = D.d_query;
             la.matrix = merge ? (const int64_t*)(dup + kUpExactMat) : D.d_matrix;
             la.scores = a.scores;
+            la.pitch = pitch;
             la.m = (uint32_t)m;
             la.alpha = merge ? D.alpha : A;
             la.gap_open = Q;
@@ -2163,7 +2229,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             if (want_counts && nw) {
                 const int64_t n4max = (int64_t)D.group_ncols[0];
                 int64_t hi = maxM;                         // incl. the padding code 0 (as FlagArgs::maxm)
-                for (size_t i = 0; i < m; i++) hi = std::max(hi, M[qv.seq[i]]);
+                for (size_t i = 0; i < m; i++) hi = std::max<int64_t>(hi, qv.seq ? M[qv.seq[i]] : qv.prof[i * 32]);
                 for (int b = 0; b < 2; b++) {
                     const int64_t imin = b ? -32768 : -128, imax = b ? 32767 : 127;
                     if ((bw == BIT_WIDTH_8) || b == 1)
@@ -2268,6 +2334,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
             ta.query = D.d_query;
             ta.matrix = D.d_matrix;
             ta.out = dqpt;
+            ta.pitch = pitch;
             ta.m = (uint32_t)m;
             ta.alpha = A;
             ta.np = (uint32_t)pnp;
@@ -2405,7 +2472,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                             for (size_t i = 0; i < m; i++) {
                                 int64_t best = 0;
                                 for (uint32_t c = 0; c < A; c++)
-                                    best = std::max(best, vp.crow[(size_t)c * 32 + qv.seq[i]]);
+                                    best = std::max(best, vp.at(qv, c, i));
                                 (i < row_b ? top : rem) += best;
                             }
                             ta.prune_rem[p] = (uint32_t)std::min<int64_t>(rem, 1 << 30);
@@ -2601,7 +2668,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
                 // "ordinary" widths are decided from exact values and bounds
                 int64_t lo = minM, hi = maxM, pm = INT64_MIN;
                 for (size_t i = 0; i < m; i++) {
-                    const int64_t x = M[qv.seq[i]];           // padding code 0
+                    const int64_t x = qv.seq ? M[qv.seq[i]] : (int64_t)qv.prof[i * 32];   // padding code 0
                     lo = std::min(lo, x);
                     hi = std::max(hi, x);
                     pm = std::max(pm, x);
@@ -3082,6 +3149,7 @@ static bool device_search_once(DeviceDB& D, const std::vector<QueryView>& views,
 void device_search(DeviceDB& D, const std::vector<QueryView>& views, int algo, size_t k, int bw, SearchScores& out,
                    std::vector<SearchScores>* indep, bool allow_prune, const int64_t* above) {
     if (above) allow_prune = false;      // (a threshold search observes every exact score)
+    if (!views.empty() && !views[0].seq && views[0].prof) allow_prune = false;   // (nor is a profile view pruned)
     if (device_search_once(D, views, algo, k, bw, out, indep, false, allow_prune, above)) {
         out.part_retries = 0;
         return;

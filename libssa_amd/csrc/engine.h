@@ -230,6 +230,7 @@ struct SearchScores {
     // device-side timing and counts of this search (published to stats())
     double kernel_ms = 0, wide_ms = 0, d2h_ms = 0, prep_ms = 0, upload_ms = 0, sync_wait_ms = 0;
     uint64_t wide_count = 0, kernel_bytes = 0;
+    uint64_t upload_bytes = 0;           // view 0's per-search upload: the block and the strip kernels' table
     const char* kernel = "";
     uint32_t strip_rows = 0;             // pair kernel main strip height
     uint32_t long_entries = 0;           // entries the long-entry kernels scored (view 0)
@@ -268,6 +269,13 @@ struct SearchScores {
 // caller re-checks at 64 bits), or, with option "above_filter" 0, option
 // "no_filter" 1 or a query view without rows, as the full score vector.  k
 // is not used; nothing is pruned, merged or ordered
+// A profile view (QueryView::prof, ssa_amd_search_profile) comes alone: one
+// view, no batch.  Every kernel reads its scores P(c, i) from the uploaded
+// [kernel code][row pitch] table instead of matrix and query codes (kernels.h
+// prof_val); residue classes are the DB codes whose profile columns agree.
+// Switched off for it (each may be lifted later): top-k pruning and promotion
+// (allow_prune is ignored), the rare-code merge, fused batches, and the
+// overflow-counter kernels (pass BIT_WIDTH_64).
 void device_search(DeviceDB& D, const std::vector<QueryView>& views, int algo, size_t k, int bw, SearchScores& out,
                    std::vector<SearchScores>* indep = nullptr, bool allow_prune = false,
                    const int64_t* above = nullptr);

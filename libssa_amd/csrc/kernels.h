@@ -259,8 +259,27 @@ struct LongArgs {
     uint32_t* zero;
     uint32_t nzero;
     uint32_t* zero2[2];
+    // a profile view (prof_val below): `matrix` holds [alpha][pitch] position scores and
+    // `query` is not read; 0: the matrix and the query codes
+    uint32_t pitch;
 };
 constexpr int kLongWaves = 4;
+
+// Score of kernel code c at query row i, as every kernel that stages a profile
+// reads it: the matrix entry of the row's residue, matrix[(c << 5) + query[i]],
+// or -- PROF: a profile view (ssa_amd_search_profile), pitch > 0 -- the
+// position's own score, matrix[c * pitch + i].  The choice is the same for
+// every lane of a launch.  The long-entry kernels and wide_kernel take it as a
+// template flag, so their matrix forms are instruction for instruction what
+// they were before profiles existed; pair_tables_kernel, which has no column
+// loop, branches once on the scalar pitch.  Staging code only: once per strip,
+// pass or entry, never per cell.
+template <bool PROF>
+__device__ __forceinline__ int64_t prof_val(const int64_t* matrix, const uint8_t* query, uint32_t pitch, uint32_t c,
+                                            uint32_t i) {
+    if constexpr (PROF) return matrix[(size_t)c * pitch + i];
+    else return matrix[(c << 5) + query[i]];
+}
 
 struct WideArgs {
     const uint4* res;
@@ -279,6 +298,7 @@ struct WideArgs {
     uint32_t* zero;            // nzero dwords cleared by block 0 (the next filter pass's counters)
     uint32_t nzero;
     uint32_t* zero2[2];        // and these two dwords (the overflow-flag replay lists' counts), if set
+    uint32_t pitch;            // a profile view's row pitch (prof_val); 0: matrix and query codes
 };
 
 // Device-side top-k candidate filter (single query view, k <= kFilterMaxK).
@@ -520,6 +540,7 @@ struct TableArgs {
     // prune_mask_n mask words at prune_blk + kPruneWords + prune_mask, and
     // block 0 leaves `query` and `matrix` at kPruneQuery / kPruneMatrix
     uint32_t prune_mask, prune_mask_n;
+    uint32_t pitch;            // a profile view's row pitch (prof_val); 0: matrix and query codes
 };
 hipError_t launch_pair_tables(const TableArgs& a, hipStream_t st);
 // dst (device) <- src (pinned host), bytes a multiple of 4: a kernel on st

@@ -381,6 +381,10 @@ strip_f16m_kernel(const StripArgs a) {
 
 // Exact int64 re-score of overflowed lanes: the reference's 64-bit
 // recurrences verbatim (one lane per sequence, H/E column in HBM scratch).
+// PROF: a profile view (WideArgs::pitch > 0) -- the residue's row of position
+// scores is read by row index; a template flag, so the matrix form's row loop
+// is what it was.
+template <bool PROF>
 __global__ void __launch_bounds__(64) wide_kernel(const WideArgs a) {
     if (blockIdx.x == 0 && threadIdx.x < a.nzero) a.zero[threadIdx.x] = 0;
     if (blockIdx.x == 0 && threadIdx.x >= 62 && a.zero2[threadIdx.x - 62]) *a.zero2[threadIdx.x - 62] = 0;
@@ -400,12 +404,12 @@ __global__ void __launch_bounds__(64) wide_kernel(const WideArgs a) {
             for (uint32_t q = 0; q < a.m; q++) { he[2 * q] = 0; he[2 * q + 1] = 0; }
             for (uint32_t j = 0; j < len; j++) {
                 const uint32_t d = base[(size_t)(j >> 4) * 1024 + (j & 15)];
-                const int64_t* mrow = a.matrix + (d << 5);
+                const int64_t* mrow = PROF ? a.matrix + (size_t)d * a.pitch : a.matrix + (d << 5);
                 int64_t h = 0, f = 0;
                 for (uint32_t q = 0; q < a.m; q++) {
                     const int64_t nd = he[2 * q];
                     int64_t e = he[2 * q + 1];
-                    h += mrow[a.query[q]];
+                    h += PROF ? mrow[q] : mrow[a.query[q]];
                     if (e > h) h = e;
                     if (f > h) h = f;
                     if (h < 0) h = 0;
@@ -428,13 +432,13 @@ __global__ void __launch_bounds__(64) wide_kernel(const WideArgs a) {
             }
             for (uint32_t j = 0; j < len; j++) {
                 const uint32_t d = base[(size_t)(j >> 4) * 1024 + (j & 15)];
-                const int64_t* mrow = a.matrix + (d << 5);
+                const int64_t* mrow = PROF ? a.matrix + (size_t)d * a.pitch : a.matrix + (d << 5);
                 int64_t f = 2 * Q + (int64_t)(j + 2) * R;
                 int64_t h = j == 0 ? 0 : Q + (int64_t)j * R;
                 for (uint32_t q = 0; q < a.m; q++) {
                     const int64_t nd = he[2 * q];
                     int64_t e = he[2 * q + 1];
-                    h += mrow[a.query[q]];
+                    h += PROF ? mrow[q] : mrow[a.query[q]];
                     if (f > h) h = f;
                     if (e > h) h = e;
                     he[2 * q] = h;
@@ -1042,7 +1046,7 @@ hipError_t launch_filter(const FilterArgs& a, hipStream_t st) {
 // per dword, replacing a host build + a ~400 KB upload per search.
 __device__ __forceinline__ int32_t table_val(const TableArgs& a, uint32_t c, uint32_t i) {
     if (c >= a.alpha || i >= a.m) return (int32_t)(int16_t)a.pad;
-    int64_t v = a.matrix[(c << 5) + a.query[i]] + a.rel;
+    int64_t v = (a.pitch ? prof_val<true>(a.matrix, a.query, a.pitch, c, i) : prof_val<false>(a.matrix, a.query, 0, c, i)) + a.rel;
     v = v < -32768 ? -32768 : (v > 32767 ? 32767 : v);
     return (int32_t)v;
 }
@@ -1281,7 +1285,7 @@ struct ProfSlice {
     uint32_t v[rl_pad(RL) / 2];
 };
 
-template <int W, int RL, bool NW, bool TRK>
+template <int W, int RL, bool NW, bool TRK, bool PROF>
 __global__ void __launch_bounds__(64 * kLongWaves) long_kernel(const LongArgs a) {
     static_assert(!TRK || NW, "extremes are an NW counter input");
     // at least the pair kernel's 168 VGPRs (kernel descriptor), for the same
@@ -1347,7 +1351,7 @@ __global__ void __launch_bounds__(64 * kLongWaves) long_kernel(const LongArgs a)
         for (uint32_t x = threadIdx.x; x < prow * CS; x += 64 * kLongWaves) {
             const uint32_t c = x / CS, rem = x % CS, sl = rem / RLP, k = rem % RLP;
             const uint32_t i = i0p + sl * RL + k;
-            ltab[x] = (c < a.alpha && k < (uint32_t)RL && i < m) ? (int16_t)a.matrix[(c << 5) + a.query[i]]
+            ltab[x] = (c < a.alpha && k < (uint32_t)RL && i < m) ? (int16_t)prof_val<PROF>(a.matrix, a.query, a.pitch, c, i)
                                                                  : (int16_t)-4096;
         }
         __syncthreads();
@@ -1655,7 +1659,7 @@ __global__ void __launch_bounds__(64 * kLongWaves) long_kernel(const LongArgs a)
 
 size_t long_lds_bytes(uint32_t alpha, int w, int rl) { return (size_t)(alpha + 1) * w * 64 * rl_pad(rl) * 2; }
 
-template <int W, int RL, bool NW, bool TRK>
+template <int W, int RL, bool NW, bool TRK, bool PROF>
 static hipError_t launch_long_k(const LongArgs& a, hipStream_t st) {
     static std::atomic<uint64_t> attr{0};
     // (the attribute leaves room for the kernel's static LDS: ring, maxima)
@@ -1669,18 +1673,18 @@ static hipError_t launch_long_k(const LongArgs& a, hipStream_t st) {
     // workgroups that cannot start (NW on the Swiss-Prot form: 2.6 ms a search)
     static const size_t static_lds = [] {
         hipFuncAttributes fa{};
-        return hipFuncGetAttributes(&fa, (const void*)long_kernel<W, RL, NW, TRK>) == hipSuccess ? fa.sharedSizeBytes
+        return hipFuncGetAttributes(&fa, (const void*)long_kernel<W, RL, NW, TRK, PROF>) == hipSuccess ? fa.sharedSizeBytes
                                                                                                   : 0;
     }();
     const size_t pad = std::min<size_t>(a.lds_min, kDynMax);
     const size_t bytes = std::max<size_t>(need, pad > static_lds ? pad - static_lds : 0);
-    const hipError_t e = lds_attr_once((const void*)long_kernel<W, RL, NW, TRK>, attr, (int)kDynMax);
+    const hipError_t e = lds_attr_once((const void*)long_kernel<W, RL, NW, TRK, PROF>, attr, (int)kDynMax);
     if (e != hipSuccess) return e;
     constexpr int EPW = kLongWaves / W;
     if (a.list && (W != 1 || a.blocks == 0 || a.hmm || a.timeline || a.gate)) return hipErrorInvalidValue;
     LongArgs b = a;
     if (!a.list) b.blocks = (a.nseq + EPW - 1) / EPW;
-    (void)ssa_launch((const void*)&long_kernel<W, RL, NW, TRK>, dim3(b.blocks), dim3(64 * kLongWaves), bytes, st, b);
+    (void)ssa_launch((const void*)&long_kernel<W, RL, NW, TRK, PROF>, dim3(b.blocks), dim3(64 * kLongWaves), bytes, st, b);
     return hipGetLastError();
 }
 
@@ -1688,9 +1692,10 @@ static hipError_t launch_long_k(const LongArgs& a, hipStream_t st) {
 template <int W, int RL, bool NW>
 static hipError_t launch_long_t(const LongArgs& a, hipStream_t st) {
     if constexpr (NW) {
-        if (a.hmm) return launch_long_k<W, RL, true, true>(a, st);
+        // (the extremes feed the overflow counters, which a profile view never runs)
+        if (a.hmm) return a.pitch ? hipErrorInvalidValue : launch_long_k<W, RL, true, true, false>(a, st);
     }
-    return launch_long_k<W, RL, NW, false>(a, st);
+    return a.pitch ? launch_long_k<W, RL, NW, false, true>(a, st) : launch_long_k<W, RL, NW, false, false>(a, st);
 }
 
 hipError_t launch_long(const LongArgs& a, int w, int rl, bool nw, hipStream_t st) {
@@ -1791,6 +1796,7 @@ __device__ __forceinline__ int32_t wave_prefix_max(int32_t x) {
 __device__ __forceinline__ int32_t wave_shr1(int32_t x, int32_t lane0) {
     return __builtin_amdgcn_update_dpp(lane0, x, 0x138, 0xf, 0xf, false);    // wave_shr:1, lane 0 <- lane0
 }
+template <bool PROF>
 __device__ int32_t long16_rows(const LongArgs& a, uint32_t* scr, const uint4* rp, uint32_t n, uint32_t m0, int lane) {
     const int32_t base = (int32_t)a.base16;
     const int32_t Q = a.gap_open, R = a.gap_extend, Rabs = -R;
@@ -1804,10 +1810,12 @@ __device__ int32_t long16_rows(const LongArgs& a, uint32_t* scr, const uint4* rp
     for (uint32_t r = m0; r < a.m; r++) {
         // (the previous row's stores before this row's loads of the same words)
         if (r > m0) __threadfence();
-        const uint32_t qr = a.query[r];
         const bool feeds = r + 1 < a.m;
-        // lane c: M[c][q_r] (c < 32; the padding code's row too)
-        const int32_t mrow = lane < 32 ? (int32_t)a.matrix[((uint32_t)lane << 5) + qr] : 0;
+        // lane c: M[c][q_r] (c < 32; the padding code's row too), or a profile's
+        // row r (its codes only: the padding code's value is never used, `valid`)
+        int32_t mrow;
+        if constexpr (PROF) mrow = (uint32_t)lane < a.alpha ? (int32_t)a.matrix[(size_t)lane * a.pitch + r] : -1;
+        else mrow = lane < 32 ? (int32_t)a.matrix[((uint32_t)lane << 5) + a.query[r]] : 0;
         int32_t carry_m = 0;                          // max of H~ over the columns so far (H~(-1) = 0)
         int32_t carry_h = 0;                          // H(r-1, c0-1): the diagonal input of lane 0
         uint32_t pk_n = load_pk((uint32_t)lane);
@@ -1848,7 +1856,7 @@ __device__ int32_t long16_rows(const LongArgs& a, uint32_t* scr, const uint4* rp
     return best;
 }
 
-template <int RL>
+template <int RL, bool PROF>
 __global__ void __launch_bounds__(64 * kLongWaves) long16_kernel(const LongArgs a) {
     static_assert(RL % 2 == 0, "rows per lane come in register pairs");
     asm volatile("" ::: "v167");                     // as long_kernel: a pair wave fits where it ran
@@ -1895,8 +1903,8 @@ __global__ void __launch_bounds__(64 * kLongWaves) long16_kernel(const LongArgs 
             uint32_t v = padw;
             if (k < (uint32_t)NR && c < a.alpha) {
                 const uint32_t lo = i0p + sl * RL + k, hi = lo + NR;
-                const uint32_t vl = lo < m ? (uint32_t)(uint16_t)(int16_t)a.matrix[(c << 5) + a.query[lo]] : padw & 0xffffu;
-                const uint32_t vh = hi < m ? (uint32_t)(uint16_t)(int16_t)a.matrix[(c << 5) + a.query[hi]] : padw & 0xffffu;
+                const uint32_t vl = lo < m ? (uint32_t)(uint16_t)(int16_t)prof_val<PROF>(a.matrix, a.query, a.pitch, c, lo) : padw & 0xffffu;
+                const uint32_t vh = hi < m ? (uint32_t)(uint16_t)(int16_t)prof_val<PROF>(a.matrix, a.query, a.pitch, c, hi) : padw & 0xffffu;
                 v = vl | (vh << 16);
             }
             ptab[x] = v;
@@ -2079,7 +2087,7 @@ __global__ void __launch_bounds__(64 * kLongWaves) long16_kernel(const LongArgs 
     int32_t score = (int32_t)smax - (int32_t)a.base16;
     if (a.extra16 && active && n > 0) {
         __threadfence();                             // the last pass's scratch row, visible to every lane
-        score = max(score, long16_rows(a, scr, rp, n, m, lane));
+        score = max(score, long16_rows<PROF>(a, scr, rp, n, m, lane));
     }
     if (active && lane == 0) {
         const uint32_t o = a.lane_out[ss];
@@ -2091,20 +2099,20 @@ __global__ void __launch_bounds__(64 * kLongWaves) long16_kernel(const LongArgs 
 
 size_t long16_lds_bytes(uint32_t alpha, int rl) { return (size_t)(alpha + 1) * 64 * long16_slot(rl) * 4; }
 
-template <int RL>
+template <int RL, bool PROF>
 static hipError_t launch_long16_k(const LongArgs& a, hipStream_t st) {
     static std::atomic<uint64_t> attr{0};
     constexpr size_t kDynMax = kPairLdsMax - 8192;
     const size_t need = long16_lds_bytes(a.alpha, RL);
     if (need > kDynMax) return hipErrorInvalidValue;
     const size_t bytes = std::max<size_t>(need, std::min<size_t>(a.lds_min, kDynMax));
-    const hipError_t e = lds_attr_once((const void*)long16_kernel<RL>, attr, (int)kDynMax);
+    const hipError_t e = lds_attr_once((const void*)long16_kernel<RL, PROF>, attr, (int)kDynMax);
     if (e != hipSuccess) return e;
     // (four entries per workgroup: eight measured -8 % on Swiss-Prot,
     // profiles/r05/ab/l16w8_sprot -- a finished workgroup's hole waits for
     // its longest entry, and more prio-3 waves starve the pair waves beside them)
     const uint32_t blocks = (a.nseq + kLongWaves - 1) / kLongWaves;
-    (void)ssa_launch((const void*)&long16_kernel<RL>, dim3(blocks), dim3(64 * kLongWaves), bytes, st, a);
+    (void)ssa_launch((const void*)&long16_kernel<RL, PROF>, dim3(blocks), dim3(64 * kLongWaves), bytes, st, a);
     return hipGetLastError();
 }
 
@@ -2112,12 +2120,12 @@ hipError_t launch_long16(const LongArgs& a, int rl, hipStream_t st) {
     if (a.nseq == 0) return hipSuccess;
     if (a.alpha > 32 || a.base16 < 0x0400u || a.base16 > 0x7BFFu) return hipErrorInvalidValue;
     switch (rl) {
-        case 4: return launch_long16_k<4>(a, st);
-        case 6: return launch_long16_k<6>(a, st);
-        case 8: return launch_long16_k<8>(a, st);
-        case 10: return launch_long16_k<10>(a, st);
-        case 12: return launch_long16_k<12>(a, st);
-        case 16: return launch_long16_k<16>(a, st);
+        case 4: return a.pitch ? launch_long16_k<4, true>(a, st) : launch_long16_k<4, false>(a, st);
+        case 6: return a.pitch ? launch_long16_k<6, true>(a, st) : launch_long16_k<6, false>(a, st);
+        case 8: return a.pitch ? launch_long16_k<8, true>(a, st) : launch_long16_k<8, false>(a, st);
+        case 10: return a.pitch ? launch_long16_k<10, true>(a, st) : launch_long16_k<10, false>(a, st);
+        case 12: return a.pitch ? launch_long16_k<12, true>(a, st) : launch_long16_k<12, false>(a, st);
+        case 16: return a.pitch ? launch_long16_k<16, true>(a, st) : launch_long16_k<16, false>(a, st);
         default: return hipErrorInvalidValue;
     }
 }
@@ -2160,7 +2168,8 @@ hipError_t launch_pair(const StripArgs& a, int np, int npt, bool nw, size_t lds_
 
 hipError_t launch_wide(const WideArgs& a, uint32_t threads, hipStream_t st) {
     const uint32_t blocks = (threads + 63) / 64;
-    (void)ssa_launch((const void*)&wide_kernel, dim3(blocks), dim3(64), 0, st, a);
+    (void)ssa_launch(a.pitch ? (const void*)&wide_kernel<true> : (const void*)&wide_kernel<false>, dim3(blocks), dim3(64), 0,
+                     st, a);
     return hipGetLastError();
 }
 
